@@ -15,9 +15,13 @@ reference checkpoint layout (no checkpoints offline), fp16 storage / fp32 accumu
 N > 1 (one process per GPU): default ``--mode shard`` partitions ONE clip over the ranks -- 2-way CFG x N/2 frame
 shards with RCCL exchanges only at the temporal ops (mofa_video_amd/parallel.py; strong scaling) -- and
 ``--mode replicas`` runs one independent clip per rank (weak scaling).  The barrier + max-over-ranks timing contract
-is kept in both.  Rank 0 prints ONE JSON line with the extra
-``roofline`` (dominant kernel = MFMA implicit-GEMM, timed per launch with HIP events on the launch stream during
-the timed region) and ``cpu_baseline`` (the CPU oracle on a bounded sample) objects.
+is kept in both.  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set-up, warm-up, the K timed clips (``ms_per_step`` = one clip).
+``--full`` adds the figures beside it, as separate legs: ``roofline`` (dominant kernel = MFMA implicit-GEMM, timed per
+launch with HIP events on the launch stream during the last timed clip, which then runs single-stream) and
+``cpu_baseline`` (the CPU oracle on a bounded sample, a child process of up to 7 minutes).
+``--dump-outputs DIR`` writes the frames of the last timed clip as float .npy files (``dump_outputs``).
 """
 import argparse
 import json
@@ -358,6 +362,87 @@ def cpu_baseline(timeout=420):
                         f"--cpu-baseline-full, several minutes)"))
 
 
+def roofline_leg(timer, clip_ms):
+    """--full: the ``roofline`` object from the HIP-event durations of the last timed clip (``timer``) and the newest
+    committed PMC traffic summary under profiles/"""
+    summ = timer.summary()
+    ig = summ.get("igemm_f16_kernel", dict(launches=1, seconds=1.0, flops=0.0))
+    avg_s = ig["seconds"] / max(ig["launches"], 1)
+    ach = ig["flops"] / ig["seconds"] / 1e12
+    at = summ.get("attn_spatial_kernel")
+    traffic = None       # HBM bytes per launch from the committed PMC passes (not collectable live)
+    import glob
+    tags = sorted((os.path.basename(f).split("_")[0] for f in glob.glob(os.path.join(ROOT, "profiles", "r*_igemm_traffic.json"))),
+                  reverse=True)
+    for tag in tags:                                              # newest committed PMC summary (tools/profile_round.sh)
+        try:
+            tj = json.load(open(os.path.join(ROOT, "profiles", f"{tag}_igemm_traffic.json")))
+            traffic = dict(hbm_bytes_per_launch=round(tj["hbm_bytes_per_launch"]),
+                           source=f"profiles/{tag}_igemm_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate "
+                                  "passes, gfx950 x2 FETCH correction)")
+            break
+        except Exception:  # noqa: BLE001
+            pass
+    roofline = dict(kernel="igemm_f16_kernel (+ ff320_kernel: the level-0 feed-forward GEMM pairs, fused with their LayerNorm / GELU / residuals)", bound="mfma", achieved=round(ach, 1), peak=MFMA_PEAK_TFLOPS,
+                    unit="TFLOP/s", frac=round(ach / MFMA_PEAK_TFLOPS, 4), traffic=traffic,
+                    launches_per_clip=ig["launches"],
+                    timed_with_events="the last of the K timed clips, run in single-stream order (exclusive kernel durations)",
+                    avg_launch_us=round(avg_s * 1e6, 1),
+                    algorithmic_tflop_per_launch=round(ig["flops"] / max(ig["launches"], 1) / 1e12, 5),
+                    share_of_clip_time=round(ig["seconds"] / (clip_ms[-1] * 1e-3), 3))
+    if at:
+        roofline["attn_spatial_kernel"] = dict(achieved=round(at["flops"] / at["seconds"] / 1e12, 1), unit="TFLOP/s",
+                                               frac=round(at["flops"] / at["seconds"] / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                                               share_of_clip_time=round(at["seconds"] / (clip_ms[-1] * 1e-3), 3))
+    # HBM-bound kernels of the adapter on REAL bytes (8 TB/s peak HBM bandwidth of the MI355X): the forward-splat warp
+    # (count / scan / fill / sort / gather, timed as one op; bytes = per flow frame and target pixel: C fp16 read + C fp16
+    # written + the flow + its CSR entries) and the full-resolution 16 / 32-channel condition-embedding convolutions (rows x
+    # (64 padded input channels + N output channels) x 2 B)
+    hbm = {}
+    ss = summ.get("softsplat_avg")
+    if ss and ss["seconds"] > 0:
+        hbm["softsplat_avg (ss_count/scan/fill/sort/gather)"] = dict(
+            achieved=round(ss["bytes"] / ss["seconds"] / 1e9, 1), peak=8000.0, unit="GB/s",
+            frac=round(ss["bytes"] / ss["seconds"] / 8e12, 4), launches=ss["launches"])
+    small = [(tag, v) for tag, v in timer.by_tag().items() if tag[4] <= 32 and tag[3] >= 100000]
+    if small:
+        by = sum(v[0] * tag[3] * (64 + tag[4]) * 2.0 for tag, v in small)
+        sec = sum(v[1] for tag, v in small)
+        hbm["igemm_f16_kernel, full-resolution 16/32-channel adapter convolutions"] = dict(
+            achieved=round(by / sec / 1e9, 1), peak=8000.0, unit="GB/s", frac=round(by / sec / 8e12, 4),
+            launches=sum(v[0] for _, v in small))
+    if hbm:
+        roofline["hbm_kernels"] = hbm
+    return roofline
+
+
+DUMP_SAMPLE = 1 << 23       # values of a frames tensor kept by --dump-outputs (32 MB of float32)
+
+
+def dump_outputs(frames, out_dir):
+    """--dump-outputs: what the caller of the timed path received from its last clip -- ``frames``, the "pt" output of the
+    batch-1 clip: fp32 [N,3,H,W] in [0, 1] -- as .npy files under out_dir, 64 MB at most:
+      frames_sample.npy    float32 [DUMP_SAMPLE]: the values at DUMP_SAMPLE flat positions of the C-order array, drawn
+                           without replacement by a CPU generator seeded 0 and sorted (the same positions on every run of
+                           the same shape; the whole tensor when it is not larger);
+      frames_row_mean.npy  float64 [N,3,H]: the mean of every image row, so that every value has a say.
+    Compare dumps of runs with the same options: under --full the last clip runs single-stream, whose half-size launches
+    pick other tiles (a few 1e-3 apart from the default order).  Returns the list of files written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = frames.float().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        pos = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+        flat = flat[pos.to(flat.device)]
+    written = []
+    for name, a in (("frames_sample", flat.cpu().numpy().astype(np.float32)),
+                    ("frames_row_mean", frames.double().mean(dim=-1).cpu().numpy())):
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        written.append(path)
+    return written
+
+
 def spawn_command(n, argv, port):
     """The command line `python bench.py --gpus N ...` re-executes itself under: one process per GPU, torch.distributed.run on
     the loopback address (the driver's own launch line for N > 1)."""
@@ -388,13 +473,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline leg (HIP events on every launch of the last "
+                         "timed clip, which then runs single-stream; the committed PMC traffic summary) and the CPU-oracle "
+                         "baseline (config 2, one GPU; a child process of up to 7 minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed clips, write the frames the last one returned as float .npy files under DIR "
+                         "(a seeded sample + every row mean, 64 MB at most; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--cpu-baseline-full", action="store_true",
                     help="no GPU work: time ONE full-size denoise step of the CPU oracle (25 f 576x1024; several minutes) and print "
                          "the cpu_baseline object it yields (kept under profiles/)")
     ap.add_argument("--no-launch-timer", action="store_true",
-                    help="A/B switch: do not bracket the launches with HIP events (the line then carries no live roofline leg); "
-                         "measures what the event records cost inside the timed region")
+                    help="A/B switch for --full: do not bracket the launches with HIP events (the line then carries no live "
+                         "roofline leg); measures what the event records cost inside the timed region")
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4, 5],
                     help="BASELINE.json configs[config - 1]: 2 = Traj (the headline metric's configuration, default), "
                          "3 = Keypoint, 4 = Hybrid, 5 = 97-frame long video with hybrid control (about a minute per clip)")
@@ -420,6 +512,9 @@ def main():
     if args.cpu_baseline_full:
         print(json.dumps(cpu_baseline_full()))
         return
+    if args.dump_outputs and args.gpus > 1 and args.mode == "shard":
+        raise SystemExit("bench.py: --dump-outputs needs one whole clip per rank (--gpus 1 or --mode replicas); in shard mode "
+                         "every rank holds only the VAE chunks it decoded")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))    # plain `python bench.py --gpus N`: N ranks, never a silent 1-GPU run
@@ -513,14 +608,16 @@ def main():
     #    the CUs the other stream's kernel holds, so it no longer measures the kernel: the per-launch durations are taken with
     #    nothing running beside (the same mode as profiles/archive/r03*_kernel_stats_bench.md, `--single-stream`).
     # `value` is still all K clips / the whole timed region, the instrumented one included; config.clip_ms has both kinds.
+    # The leg is part of --full only: a plain run times K clips in the default order and nothing else.
     timer = ops.LaunchTimer()
+    instrument = args.full and not args.no_launch_timer
     pipe.overlap_adapter = not args.single_stream
     clip_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     barrier()
     t0 = time.perf_counter()
     clip_ev[0].record()
     for i in range(args.steps):
-        if i == args.steps - 1 and not args.no_launch_timer:
+        if i == args.steps - 1 and instrument:
             ops.TIMER, pipe.overlap_adapter = timer, False
         frames = run_config(pipe, inp, cfg)
         clip_ev[i + 1].record()
@@ -538,54 +635,9 @@ def main():
         dt = float(tt.item())
 
     if rank == 0:
-        summ = timer.summary()
-        ig = summ.get("igemm_f16_kernel", dict(launches=1, seconds=1.0, flops=0.0))
-        avg_s = ig["seconds"] / max(ig["launches"], 1)
-        ach = ig["flops"] / ig["seconds"] / 1e12
-        at = summ.get("attn_spatial_kernel")
-        traffic = None       # HBM bytes per launch from the committed PMC passes (not collectable live)
-        import glob
-        tags = sorted((os.path.basename(f).split("_")[0] for f in glob.glob(os.path.join(ROOT, "profiles", "r*_igemm_traffic.json"))),
-                      reverse=True)
-        for tag in tags:                                              # newest committed PMC summary (tools/profile_round.sh)
-            try:
-                tj = json.load(open(os.path.join(ROOT, "profiles", f"{tag}_igemm_traffic.json")))
-                traffic = dict(hbm_bytes_per_launch=round(tj["hbm_bytes_per_launch"]),
-                               source=f"profiles/{tag}_igemm_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate "
-                                      "passes, gfx950 x2 FETCH correction)")
-                break
-            except Exception:  # noqa: BLE001
-                pass
-        roofline = dict(kernel="igemm_f16_kernel (+ ff320_kernel: the level-0 feed-forward GEMM pairs, fused with their LayerNorm / GELU / residuals)", bound="mfma", achieved=round(ach, 1), peak=MFMA_PEAK_TFLOPS,
-                        unit="TFLOP/s", frac=round(ach / MFMA_PEAK_TFLOPS, 4), traffic=traffic,
-                        launches_per_clip=ig["launches"],
-                        timed_with_events="the last of the K timed clips, run in single-stream order (exclusive kernel durations)",
-                        avg_launch_us=round(avg_s * 1e6, 1),
-                        algorithmic_tflop_per_launch=round(ig["flops"] / max(ig["launches"], 1) / 1e12, 5),
-                        share_of_clip_time=round(ig["seconds"] / (clip_ms[-1] * 1e-3), 3))
-        if at:
-            roofline["attn_spatial_kernel"] = dict(achieved=round(at["flops"] / at["seconds"] / 1e12, 1), unit="TFLOP/s",
-                                                   frac=round(at["flops"] / at["seconds"] / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                                                   share_of_clip_time=round(at["seconds"] / (clip_ms[-1] * 1e-3), 3))
-        # HBM-bound kernels of the adapter on REAL bytes (8 TB/s peak; MI355X_MICROARCH.md): the forward-splat warp
-        # (count / scan / fill / sort / gather, timed as one op; bytes = per flow frame and target pixel: C fp16 read + C fp16
-        # written + the flow + its CSR entries) and the full-resolution 16 / 32-channel condition-embedding convolutions (rows x
-        # (64 padded input channels + N output channels) x 2 B)
-        hbm = {}
-        ss = summ.get("softsplat_avg")
-        if ss and ss["seconds"] > 0:
-            hbm["softsplat_avg (ss_count/scan/fill/sort/gather)"] = dict(
-                achieved=round(ss["bytes"] / ss["seconds"] / 1e9, 1), peak=8000.0, unit="GB/s",
-                frac=round(ss["bytes"] / ss["seconds"] / 8e12, 4), launches=ss["launches"])
-        small = [(tag, v) for tag, v in timer.by_tag().items() if tag[4] <= 32 and tag[3] >= 100000]
-        if small:
-            by = sum(v[0] * tag[3] * (64 + tag[4]) * 2.0 for tag, v in small)
-            sec = sum(v[1] for tag, v in small)
-            hbm["igemm_f16_kernel, full-resolution 16/32-channel adapter convolutions"] = dict(
-                achieved=round(by / sec / 1e9, 1), peak=8000.0, unit="GB/s", frac=round(by / sec / 8e12, 4),
-                launches=sum(v[0] for _, v in small))
-        if hbm:
-            roofline["hbm_kernels"] = hbm
+        if args.dump_outputs:
+            files = dump_outputs(frames[0], args.dump_outputs)     # the list of one clip's frames (batch 1)
+            print(f"[bench] last timed clip's outputs: {', '.join(files)}", file=sys.stderr)
         clips = args.steps * (world if mode == "replicas" else 1)
         nfr = LONG_FRAMES if cfg == 5 else T
         value = nfr * clips / dt
@@ -613,17 +665,18 @@ def main():
                        "decode_chunk_size": CHUNK, "step_definition": "one whole clip from the conditioning image (CLIP + VAE "
                        "encode, adapter prep, 25 denoise steps, VAE decode)", "parallelism": par_desc,
                        "streams": ("single stream" if args.single_stream else
-                                   "adapter trunk || UNet encoder, then the decoder's two CFG halves, on two HIP streams; the last timed clip (HIP "
-                                   "events) single-stream"),
+                                   "adapter trunk || UNet encoder, then the decoder's two CFG halves, on two HIP streams" +
+                                   ("; the last timed clip (HIP events) single-stream" if instrument else "")),
                        "graph_steps": bool(pipe.graph_steps), **({"gn_stats": bool(args.gn_stats)} if args.gn_stats >= 0 else {}),
                        **({"ff_fused": bool(args.ff_fused)} if args.ff_fused >= 0 else {}),
                        "clip_ms": clip_ms,
                        "output_finite": finite, "comm_paths": comm_paths, **({"library": args.lib} if args.lib else {}),
                        "effective_tflops_per_gpu_reference_work_model": round(CLIP_TFLOPS[cfg] * clips / dt / world, 1)},
-            "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline and cfg == 2:
-            line["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            line["roofline"] = roofline_leg(timer, clip_ms)
+            if world == 1 and not args.no_cpu_baseline and cfg == 2:
+                line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line))
     if dist is not None:
         dist.barrier()

@@ -8,7 +8,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $O
 export MOFA_BENCH_ONE_GPU=1 HSA_ENABLE_IPC_MODE_LEGACY=0
 run() {  # world config steps
   MOFA_BENCH_DENOISE_STEPS=$3 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $1 --master-addr 127.0.0.1 \
-    --master-port $((29500 + $1 * 10 + $2)) bench.py --gpus $1 --config $2 --backend gloo --steps 1 --warmup 0 --no-cpu-baseline \
+    --master-port $((29500 + $1 * 10 + $2)) bench.py --gpus $1 --config $2 --backend gloo --steps 1 --warmup 0 --full --no-cpu-baseline \
     > $O/${TAG}_functional_gloo$1_cfg$2.log 2>&1
   tail -1 $O/${TAG}_functional_gloo$1_cfg$2.log > $O/${TAG}_functional_shard_gloo$1_cfg$2.json
   python - <<PY
