@@ -34,9 +34,6 @@ __device__ __forceinline__ f16x4 lds_read_tr4(const f16* p) {
     return __builtin_bit_cast(f16x4, v);
 }
 
-#ifndef ATT_NBUF_D
-#define ATT_NBUF_D 2   // (3: K / V tiles fetched two ahead -- bit-identical, measured 1-2 % slower, profiles/r06_attn_anatomy.log)
-#endif
 template <int D, int QB>
 __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
                                                               const f16* __restrict__ v, f16* __restrict__ out,
@@ -49,10 +46,10 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restr
     // swapped in rows with bit 1 set (the 4 key rows x 64 bytes of a transpose read then cover 4 distinct bank quarters).
     // D = 128 (0.1 % of a clip) keeps the register-staged, padded form.
     constexpr bool DMA = D == 64;
-    // DMA form: ATT_NBUF_D = 2 buffers, tile t + 1 fetched while tile t is computed.  (-DATT_NBUF_D=3: a ring of three, fetched TWO
-    // tiles ahead with a counted end-of-tile wait -- the landing time of a piece is NOT what the end-of-tile wait stalls on: same
-    // results bit for bit, 1-2 % slower at S = 9216 and 2304, profiles/r06_attn_anatomy.log)
-    constexpr int NBUF = DMA ? ATT_NBUF_D : 2;
+    // Two buffers, tile t + 1 fetched while tile t is computed.  (A ring of three, fetched TWO tiles ahead with a counted
+    // end-of-tile wait -- the landing time of a piece is NOT what the end-of-tile wait stalls on: same results bit for bit,
+    // 1-2 % slower at S = 9216 and 2304, profiles/r06_attn_anatomy.log)
+    constexpr int NBUF = 2;
     constexpr int ATT_KSTR = DMA ? D : D + 8;
     constexpr int ATT_VSTR = DMA ? D : D + 32; // V tile row stride (halves)
     constexpr int KK = D / 16;       // MFMA k-steps of S^T
@@ -198,34 +195,20 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restr
     const int ntiles = (S + ATT_TILE - 1) / ATT_TILE;
     if constexpr (DMA) {
         dma_tile(0, 0);
-        if (NBUF == 3 && ntiles > 1) {
-            dma_tile(1, 1);
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");        // tile 0 has landed; tile 1's four pieces stay in flight
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
         load_tile(0);
         store_tile(0);
     }
     __syncthreads();
 
-#if defined(ATT_T_NOREADK) || defined(ATT_T_NOREADV)
-    f16x8 kstale[KK];                                               // fragments read ONCE (tile 0), reused for every tile
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) kstale[kk] = *(const f16x8*)(sKb + l31 * ATT_KSTR + kk * 16 + lh * 8);
-#endif
     int buf = 0;                                                    // t % NBUF
     for (int t = 0; t < ntiles; ++t, buf = (buf + 1 == NBUF ? 0 : buf + 1)) {
         const int k0 = t * ATT_TILE;
-#ifndef ATT_T_NODMA
-        if constexpr (DMA && NBUF == 3) {
-            if (t + 2 < ntiles) dma_tile(t + 2, buf == 0 ? 2 : buf - 1);   // slot (t + 2) % 3 = (t - 1) % 3: released by the last barrier
-        } else if (t + 1 < ntiles) {
+        if (t + 1 < ntiles) {
             if constexpr (DMA) dma_tile(t + 1, buf ^ 1);            // (the other buffer was released by the last barrier)
             else load_tile(k0 + ATT_TILE);
         }
-#endif
 
         // ---- S^T tiles: s[b][ts][r] = score(key = k0 + 32*ts + (r&3) + 8*(r>>2) + 4*lh, query = 32*b + l31) ----
         // the accumulators start at -m_run: NEGM keeps that as a 16-register tuple per query block (it changes only when the
@@ -243,11 +226,7 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restr
             const f16* kp = sKb + buf * ATT_TILE * ATT_KSTR + (ts * 32 + l31) * ATT_KSTR + (DMA ? 0 : lh * 8);
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
-#ifdef ATT_T_NOREADK                           // timing-only builds (wrong results; the data flow stays): tools/attn_anatomy.sh
-                const f16x8 kf = kstale[kk];
-#else
                 const f16x8 kf = *(const f16x8*)(kp + (DMA ? ((2 * kk + lh) ^ ksw) * 8 : kk * 16));
-#endif
 #pragma unroll
                 for (int b = 0; b < QB; ++b)
                     s[b][ts] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[b][kk], (NEGM && kk == 0) ? negm[b] : s[b][ts], 0, 0, 0);
@@ -283,51 +262,10 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restr
             for (int ts = 0; ts < 2; ++ts)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-#ifdef ATT_T_NOEXP
-                    const float p = s[b][ts][r] * 1e-3f;                  // (one full-rate multiply instead of the quarter-rate v_exp_f32)
-#else
                     const float p = __builtin_amdgcn_exp2f(s[b][ts][r]);   // raw v_exp_f32
-#endif
-#if !defined(ATT_T_NOSUM) && !defined(ATT_SUM_MFMA4) && !defined(ATT_SUM_DOT2)
                     psum += p;
-#endif
                     pf[b][ts][r >> 3][r & 7] = (f16)p;
                 }
-#ifdef ATT_SUM_DOT2
-            // (experiment) v_dot2_f32_f16 against (1, 1): 16 instead of 32 instructions, fp32 accumulation of the fp16 probabilities
-            {
-                typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                const h2 one2 = {(f16)1.f, (f16)1.f};
-#pragma unroll
-                for (int ts = 0; ts < 2; ++ts)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const h2 pp = {pf[b][ts][u][2 * e], pf[b][ts][u][2 * e + 1]};
-                            psum = __builtin_amdgcn_fdot2(pp, one2, psum, false);
-                        }
-            }
-#endif
-#ifdef ATT_SUM_MFMA4
-            // (experiment, tools/attn_sum_experiment.sh) the lane's 32 probabilities summed by eight v_mfma_f32_4x4x4_16B_f16 with an all-ones
-            // A operand: every lane of a 4-lane block gets the sum of ITS OWN four fp16 values in all four result registers
-            {
-                typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-                const h4 ones = {(f16)1.f, (f16)1.f, (f16)1.f, (f16)1.f};
-                f32x4 t4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int ts = 0; ts < 2; ++ts)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        const h4 lo = {pf[b][ts][u][0], pf[b][ts][u][1], pf[b][ts][u][2], pf[b][ts][u][3]};
-                        const h4 hi = {pf[b][ts][u][4], pf[b][ts][u][5], pf[b][ts][u][6], pf[b][ts][u][7]};
-                        t4 = __builtin_amdgcn_mfma_f32_4x4x4f16(ones, lo, t4, 0, 0, 0);
-                        t4 = __builtin_amdgcn_mfma_f32_4x4x4f16(ones, hi, t4, 0, 0, 0);
-                    }
-                psum = t4[0];
-            }
-#endif
             const float ptot = psum + __shfl_xor(psum, 32, 64);           // both key halves of the query row
             const bool move = !(ptot < ATT_DEFER_SUM) || t == 0;           // (NaN-safe; tile 0: m_run = 0 is no reference yet)
             if (__any(move)) {
@@ -372,29 +310,19 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restr
             for (int ts = 0; ts < 2; ++ts)
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
-#ifdef ATT_T_NOREADV
-                    const f16x8 vf = kstale[(db + ts + u) % KK];
-#else
                     const f16x4 lo = lds_read_tr4(vp + (ts * 32 + u * 16) * ATT_VSTR);        // keys k0 + 4 lh + 0..3
                     const f16x4 hi = lds_read_tr4(vp + (ts * 32 + u * 16 + 8) * ATT_VSTR);    // keys k0 + 4 lh + 8..11
                     const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#endif
 #pragma unroll
                     for (int b = 0; b < QB; ++b) o[b][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[b][ts][u], o[b][db], 0, 0, 0);
                 }
         }
         if (t + 1 < ntiles) {
-            // this wave's pieces of tile t + 1 have landed (the loop has no other vector-memory operation: with the ring of three,
-            // the four pieces of tile t + 2 -- the youngest -- may stay in flight)
-            if constexpr (DMA && NBUF == 3) {
-                if (t + 2 < ntiles) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            } else if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // this wave's pieces of tile t + 1 have landed (the loop has no other vector-memory operation)
+            if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             else store_tile(buf ^ 1);
         }
-#ifndef ATT_T_NOBAR
         __syncthreads();
-#endif
     }
 
 #pragma unroll
@@ -420,17 +348,12 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restr
 template <int D, int QB>
 static int launch_attn_spatial(const void* q, const void* k, const void* v, void* out, int nframes, int heads, int S,
                                int ldq, int ldk, int ldv, int ldo, float c, hipStream_t st) {
-    constexpr int LDS = D == 64 ? ATT_NBUF_D * (ATT_TILE * D + ATT_TILE * D) * 2 : 2 * (ATT_TILE * (D + 8) + ATT_TILE * (D + 32)) * 2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)attn_spatial_kernel<D, QB>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) !=
-            hipSuccess)
-            return MOFA_ELAUNCH;
-        attr_set = true;
-    }
+    constexpr int LDS = D == 64 ? 2 * (ATT_TILE * D + ATT_TILE * D) * 2 : 2 * (ATT_TILE * (D + 8) + ATT_TILE * (D + 32)) * 2;
     const int nqb = cdiv(S, 128 * QB);
     const long long total = (long long)nqb * heads * nframes;
     if (total > 0x7ffffff0LL) return MOFA_EINVAL;
+    static LaunchSetup setup;
+    if (setup.cus([](int) { return mofa_lds_optin((const void*)attn_spatial_kernel<D, QB>, LDS); }) == 0) return MOFA_ELAUNCH;
     dim3 grid((unsigned)(8 * ((total + 7) / 8)));              // (the kernel's XCD-aware work order)
     hipLaunchKernelGGL((attn_spatial_kernel<D, QB>), grid, dim3(256), LDS, st, (const f16*)q, (const f16*)k, (const f16*)v,
                        (f16*)out, heads, S, ldq, ldk, ldv, ldo, c, nqb, (int)total);

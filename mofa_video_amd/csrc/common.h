@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <mutex>
 #include "../../include/mofa_hip.h"
 
 typedef _Float16 f16;
@@ -56,3 +57,38 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// One-time launch set-up of an entry point, per device.  The dynamic-LDS opt-in (hipFuncSetAttribute) is a setting of the
+// current device and the CU count a figure of it, so both are taken once per device id -- not once per process for whichever
+// device was current first -- and under std::call_once, so that several host threads can make the first launches.  cus(init)
+// returns the current device's CU count (> 0) after init(dev) -- the opt-ins, MOFA_OK or an error -- has run once for that
+// device; 0 when hipGetDevice, the CU query or init failed (the entry point returns MOFA_ELAUNCH).  *dev_out: the device id.
+// After the first launch on a device a call costs one hipGetDevice.
+constexpr int MOFA_MAX_DEVICES = 64;
+struct LaunchSetup {
+    template <typename F>
+    int cus(F&& init, int* dev_out = nullptr) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MOFA_MAX_DEVICES) return 0;
+        std::call_once(once[dev], [&] {
+            int n = 0;
+            if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 && init(dev) == MOFA_OK)
+                n_cu[dev] = n;
+        });
+        if (dev_out) *dev_out = dev;
+        return n_cu[dev];
+    }
+    int cus() { return cus([](int) { return MOFA_OK; }); }
+    std::once_flag once[MOFA_MAX_DEVICES];
+    int n_cu[MOFA_MAX_DEVICES] = {};
+};
+// dynamic-LDS opt-in of a kernel, or of every kernel of a table (null entries skipped): MOFA_OK or MOFA_ELAUNCH
+inline int mofa_lds_optin(const void* k, int bytes) {
+    return !k || hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? MOFA_OK : MOFA_ELAUNCH;
+}
+template <typename K, size_t N>
+int mofa_lds_optin(K const (&kerns)[N], int bytes) {
+    for (K k : kerns)
+        if (mofa_lds_optin((const void*)k, bytes) != MOFA_OK) return MOFA_ELAUNCH;
+    return MOFA_OK;
+}

@@ -42,15 +42,9 @@ constexpr int FF_LDS_BYTES = OFF_W2 + 2 * W2_SLOT;            // 163 840 = the w
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 template <int V> struct IC { static constexpr int v = V; };
-#ifndef FF_ILP
-#define FF_ILP 2                               // GELU pairs (2 hidden columns each) whose micro-operations alternate
-#endif
-#ifndef FF_LOOK_D
-#define FF_LOOK_D 6                            // MFMA slots a weight fragment is read ahead of its use (even)
-#endif
-#ifndef FF_BDELAY_D
-#define FF_BDELAY_D 3                          // MFMA slots into a step before the GELU reads the previous step's tiles
-#endif
+constexpr int FF_GELU_ILP = 2;                 // GELU pairs (2 hidden columns each) whose micro-operations alternate
+constexpr int FF_LOOK = 6;                     // MFMA slots a weight fragment is read ahead of its use (even)
+constexpr int FF_BDELAY = 3;                   // MFMA slots into a step before the GELU reads the previous step's tiles
 // compile-time loop: f(IC<0>{}), f(IC<1>{}), ... -- the slot schedule below needs every index as a constant expression
 template <int I, int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -61,17 +55,11 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 // step barrier: this wave's LDS-DMA pieces up to the N youngest have landed (vmcnt counts in issue order), its fragment reads are
 // back, then everybody is here.  N = the W1 pieces of the chunk two steps ahead, which may stay in flight across the barrier.
-#ifdef FF_T_NOB1
-constexpr int FF_PRE = 0;
-#else
 constexpr int FF_PRE = 8;                      // b1 loads of the next step, issued at the end of a step (see step())
-#endif
 template <int N>
 __device__ __forceinline__ void ff_barrier() {
 #if defined(FF_DBG_VM0)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#elif defined(FF_T_NOBAR)                     // timing-only build (wrong results): no step barrier at all
-    asm volatile("" ::: "memory");
 #else
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
 #endif
@@ -113,7 +101,7 @@ __global__ __launch_bounds__(256, 1) void ff320_kernel(const mofa_ff320_args a, 
     f32x16 O[FF_NJ];
     f32x16 pv[2], pg[2];
     f16x8 hf[2][2];
-    constexpr int FF_LOOK = FF_LOOK_D, FF_BDELAY = FF_BDELAY_D, FF_GOPS = 15;
+    constexpr int FF_GOPS = 15;
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     auto step = [&](auto do_a, auto do_b, auto do_c, auto par, const int chunk_a, const int slot_a, auto d1, const int chunk_w1,
                     const int slot_w1, auto d2, const int chunk_w2, auto own_b1, auto pre_b1) __attribute__((always_inline)) {
@@ -122,16 +110,8 @@ __global__ __launch_bounds__(256, 1) void ff320_kernel(const mofa_ff320_args a, 
         constexpr bool D1 = decltype(d1)::v != 0, D2 = decltype(d2)::v != 0;
         constexpr int P = decltype(par)::v;                        // k & 1: A -> p[P], B: p[P ^ 1] -> hf[P ^ 1], C: hf[P], W2 slot P
         constexpr int NC = Cc ? 2 * FF_NJ : 0, NA = A ? 2 * FF_KS : 0, NS = NC + NA;
-#ifdef FF_T_NODMA                              // timing-only builds (wrong results): no weight DMA / no GELU arithmetic / no fragment reads
-        constexpr int NPIECE = 0;
-#else
         constexpr int NPIECE = (D1 ? 10 : 0) + (D2 ? 5 : 0);
-#endif
-#ifdef FF_T_NOGELU_INVALID_DEAD_MFMA
-        constexpr int NOPS = 0;
-#else
         constexpr int NOPS = B ? 8 * FF_GOPS : 0;
-#endif
         static_assert(NS >= 20, "every step has MFMA slots");
         const char* w1 = wl + OFF_W1 + slot_a * W1_SLOT;
         const char* w2 = wl + OFF_W2 + P * W2_SLOT;
@@ -149,12 +129,8 @@ __global__ __launch_bounds__(256, 1) void ff320_kernel(const mofa_ff320_args a, 
             constexpr int PP = decltype(pc)::v;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-#ifdef FF_T_NOB1                               // timing-only: no bias loads at all
-                const f32x4 bv = {0.f, 0.f, 0.f, 0.f}, bg = {1.f, 1.f, 1.f, 1.f};
-#else
                 const f32x4 bv = *(const f32x4*)(b1l + 32 * chunk + 8 * q);
                 const f32x4 bg = *(const f32x4*)(b1l + FF_H + 32 * chunk + 8 * q);
-#endif
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { pv[PP][4 * q + e] = bv[e]; pg[PP][4 * q + e] = bg[e]; }
             }
@@ -173,7 +149,7 @@ __global__ __launch_bounds__(256, 1) void ff320_kernel(const mofa_ff320_args a, 
         for (int i = 0; i < FF_LOOK; ++i) ring[i] = frag(i);
         // GELU micro-operations of pair d (hidden registers 2 d, 2 d + 1 of p[P ^ 1]): x * Phi(x), Phi as in gelu_phi_f (common.h);
         // FF_GOPS = 15 per pair on float2 (hipcc emits scalar v_fma_f32 pairs for them, which is what is wanted: packed fp32 measured
-        // SLOWER beside the MFMAs, profiles/r06_ff320_anatomy.log), FF_ILP pairs alternating.
+        // SLOWER beside the MFMAs, profiles/r06_ff320_anatomy.log), FF_GELU_ILP pairs alternating.
         // The P^T tiles live in VGPRs, written by MFMAs issued through asm (below): hipcc keeps every accumulator of a
         // 512-register kernel in the AGPR half, and v_accvgpr_read executes IN the matrix pipe, in order with the MFMAs -- 32 reads
         // per step cost 56 % of the kernel (1413 -> 599 us with the GELU fed from ordinary registers, same log).
@@ -185,12 +161,6 @@ __global__ __launch_bounds__(256, 1) void ff320_kernel(const mofa_ff320_args a, 
             constexpr int d = decltype(dc)::v, op = decltype(oc)::v;
             constexpr float K[9] = {5.626766414e-11f, -5.371867839e-09f, 2.268295702e-07f, -5.646214049e-06f, 9.359061369e-05f,
                                     -1.109400182e-03f, 9.818118997e-03f, -6.634692103e-02f, 3.989031613e-01f};
-#ifdef FF_T_CHEAPGELU                          // timing-only: value * gate instead of value * gelu(gate): 3 of the 15 micro-operations, data flow intact
-            if constexpr (op == 0) Q[d] = f32x2{pg[P ^ 1][2 * d], pg[P ^ 1][2 * d + 1]} * f32x2{pv[P ^ 1][2 * d], pv[P ^ 1][2 * d + 1]};
-            else if constexpr (op == 13) hf[P ^ 1][d >> 2][2 * (d & 3)] = (f16)Q[d][0];
-            else if constexpr (op == 14) hf[P ^ 1][d >> 2][2 * (d & 3) + 1] = (f16)Q[d][1];
-            return;
-#endif
             if constexpr (op == 0) {
                 G[d] = f32x2{pg[P ^ 1][2 * d], pg[P ^ 1][2 * d + 1]};
                 W[d] = f32x2{__builtin_amdgcn_fmed3f(G[d][0], -4.2426405f, 4.2426405f), __builtin_amdgcn_fmed3f(G[d][1], -4.2426405f, 4.2426405f)};
@@ -228,14 +198,12 @@ __global__ __launch_bounds__(256, 1) void ff320_kernel(const mofa_ff320_args a, 
         static_for<0, NS>([&](auto ic) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::v;
             const f16x8 af = ring[i % FF_RING];
-#ifndef FF_T_NOREAD
             // reads are issued two at a time on even slots, the LATER fragment first: LDS returns in order, so the s_waitcnt in
             // front of the MFMA that needs the earlier (younger) one covers the next MFMA's too -- one wait per two MFMAs
             if constexpr ((i & 1) == 0) {
                 if constexpr (i + FF_LOOK + 1 < NS) ring[(i + FF_LOOK + 1) % FF_RING] = frag(i + FF_LOOK + 1);
                 if constexpr (i + FF_LOOK < NS) ring[(i + FF_LOOK) % FF_RING] = frag(i + FF_LOOK);
             }
-#endif
             if constexpr ((i & 1) == 0 && (i >> 1) < NPIECE) dma_piece(IC<(i >> 1)>{});   // one piece every other slot, from slot 0
             if constexpr (i < NC) {
                 O[i % FF_NJ] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, hf[P][i / FF_NJ], O[i % FF_NJ], 0, 0, 0);
@@ -253,7 +221,7 @@ __global__ __launch_bounds__(256, 1) void ff320_kernel(const mofa_ff320_args a, 
                 constexpr int mo = decltype(mc)::v;
                 // two pairs in flight, their micro-operations alternating: consecutive instructions are independent (no VALU
                 // dependency stall, and hipcc puts no s_nop between an asm statement and a following one that does not read it)
-                gelu_op(IC<FF_ILP * (mo / (FF_ILP * FF_GOPS)) + (mo % FF_ILP)>{}, IC<(mo % (FF_ILP * FF_GOPS)) / FF_ILP>{});
+                gelu_op(IC<FF_GELU_ILP * (mo / (FF_GELU_ILP * FF_GOPS)) + (mo % FF_GELU_ILP)>{}, IC<(mo % (FF_GELU_ILP * FF_GOPS)) / FF_GELU_ILP>{});
             });
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -458,16 +426,13 @@ extern "C" int mofa_ff320_f16(const mofa_ff320_args* a, mofa_stream_t stream) {
     if (a->out_ln && (!a->ln_gamma || !a->ln_beta || (a->ldoln & 7) || a->ldoln < FF_C || (((size_t)a->out_ln) & 15) ||
                       (((size_t)a->ln_gamma) & 15) || (((size_t)a->ln_beta) & 15)))
         return MOFA_EINVAL;
+    if (a->reserved[0] || a->reserved[1] || a->reserved[2] || a->reserved[3]) return MOFA_EINVAL;
     static const ff320_kern_t kerns[8] = {
         ff320_pick<false, false, false>(), ff320_pick<true, false, false>(), ff320_pick<false, true, false>(), ff320_pick<true, true, false>(),
         ff320_pick<false, false, true>(),  ff320_pick<true, false, true>(),  ff320_pick<false, true, true>(),  ff320_pick<true, true, true>()};
-    static const int n_cu = [] {
-        int dev = 0, cus = 0;
-        for (int i = 0; i < 8; ++i)
-            (void)hipFuncSetAttribute((const void*)kerns[i], hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS_BYTES);
-        return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-                cus > 0) ? cus : 256;
-    }();
+    static LaunchSetup setup;
+    const int n_cu = setup.cus([](int) { return mofa_lds_optin(kerns, FF_LDS_BYTES); });
+    if (n_cu == 0) return MOFA_ELAUNCH;
     const int ntiles = (a->M + 127) / 128;
     const int grid = ntiles < n_cu ? ntiles : n_cu;
     const ff320_kern_t k = kerns[(a->pos ? 1 : 0) | (a->r2 ? 2 : 0) | (a->out_ln ? 4 : 0)];

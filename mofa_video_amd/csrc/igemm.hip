@@ -26,13 +26,9 @@
 // row-vector loads are issued a group of passes at a time, on 128-row tiles one group ahead of the stores (vmcnt retires
 // in order on gfx9: a load issued before a store never waits for it).  The kernel is templated on the epilogue kind
 // (residuals / row vector / GEGLU) so the memory operations per pass are static.
-// Tile choice: mofa_igemm_args.tile (MOFA_TILE_*; 0 = the launcher's cost model); the environment variable
-// MOFA_IGEMM_CFG=2|4|5 forces the 128x128 | 192x128 | 256x256 phase-pipelined (igemm8.hip) tile for every launch that
-// leaves `tile` at 0.
+// Tile choice: mofa_igemm_args.tile (MOFA_TILE_*; 0 = the launcher's cost model).
 // Earlier variants (register staging, 64-byte rows, deeper rings, 256x128 tiles) and their measurements:
 // profiles/archive/r01_igemm_config_sweep.md.
-#include <stdlib.h>
-
 #include "igemm_common.h"
 
 
@@ -495,31 +491,24 @@ extern "C" int mofa_igemm_f16(const mofa_igemm_args* a, mofa_stream_t stream) {
         {IGEMM_KINDS(2, 2, 2), 128, 128, 256, 2 * 256 * 128, 2},   // 128^2 tile, 2 workgroups per CU
         {IGEMM_KINDS(2, 2, 3), 192, 128, 256, 2 * 320 * 128, 2},   // 192x128 tile: 2 x 80 KB = the whole LDS of a CU
     };
-    static bool ready = false;   // one-time set-up: LDS opt-in of every instantiation, CU count
-    static int n_cu = 256;
-    if (!ready) {
-        for (const Cfg& c : cfgs)
-            for (igemm_kern_t k : c.k)
-                if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, c.lds) != hipSuccess)
-                    return MOFA_ELAUNCH;
-        if (igemm8_init() != MOFA_OK || igemm320_init() != MOFA_OK) return MOFA_ELAUNCH;
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-            n_cu = cus >= 8 ? (cus / 8) * 8 : 8;              // persistent grids are multiples of 8 (one per XCD): every tile /
-        ready = true;                                         // round / split-K count below uses the SAME rounded figure
-    }
     if (a->tile != 0 && a->tile != MOFA_TILE_128X128 && a->tile != MOFA_TILE_192X128 && a->tile != MOFA_TILE_256X256 &&
         a->tile != MOFA_TILE_256X320)
         return MOFA_EINVAL;
+    if (a->stats && !igemm320_stats_ok(a)) return MOFA_EINVAL;   // GroupNorm pair sums from the epilogue: the 256x320 tile only
+    static LaunchSetup setup;                                 // LDS opt-in of every instantiation, CU count
+    int n_cu = setup.cus([](int) {
+        for (const Cfg& c : cfgs)
+            if (mofa_lds_optin(c.k, c.lds) != MOFA_OK) return MOFA_ELAUNCH;
+        return igemm8_init() == MOFA_OK && igemm320_init() == MOFA_OK ? MOFA_OK : MOFA_ELAUNCH;
+    });
+    if (n_cu == 0) return MOFA_ELAUNCH;
+    n_cu = n_cu >= 8 ? (n_cu / 8) * 8 : 8;                    // persistent grids are multiples of 8 (one per XCD): every tile /
+                                                              // round / split-K count below uses the SAME rounded figure
     const int taps = a->mode == MOFA_MODE_CONV3X3 ? (a->ksize > 0 ? a->ksize * a->ksize : 9) : (a->mode == MOFA_MODE_CONVT3 ? 3 : 1);
     const long long Ktot = (long long)taps * a->Cin;
     const int kind = a->act == MOFA_ACT_GEGLU_PAIR ? 8 : ((a->r1 ? 1 : 0) | (a->r2 ? 2 : 0) | (a->rowvec ? 4 : 0));
     int choice = a->tile;                                     // MOFA_TILE_* or 0 = cost model
-    if (a->stats) {                                           // GroupNorm pair sums from the epilogue: the 256x320 tile only
-        if (!igemm320_stats_ok(a)) return MOFA_EINVAL;
-        choice = MOFA_TILE_256X320;
-    }
+    if (a->stats) choice = MOFA_TILE_256X320;
     if (choice == 0) {
         // Tile choice = the cheapest of  rounds of resident workgroups x CU time of one round, the latter modelled as
         //   workgroups per CU x tile area x relative K-loop cost per flop x (1 + epilogue / K loop),  epilogue in K tiles:

@@ -31,26 +31,22 @@
 
 namespace {
 
-#ifndef STATS_D
-#define STATS_D 5
-#endif
 constexpr int WN3 = 2, MI3 = 2;                                // wave grid 4 x 2, accumulator row tiles per wave
 constexpr int TBM3 = 256;
 constexpr int RBH = 64;                                        // bytes of one K half of a row
 constexpr int XPL = TBM3 * RBH;                                // X part of a plane (16 KB)
-// NJ = accumulator column tiles per wave: 5 -> the 256x320 tile (shipped).  NJ = 4 (a 256x256 tile with the same K-half
-// schedule, incl. the GEGLU pair epilogue below) was built and measured in round 3 and is NOT instantiated: it is 5-10 %
-// SLOWER than igemm8.hip's X-row split on every shape (profiles/archive/r03_igemm_tiles_bench_with_ksplit256.log: GEGLU L0 / L1 / L2
-// 750 / 920 / 1039 against 833 / 1017 / 1141 TF/s) -- the 256x320 tile's advantage is its shape (load segment of 14 reads
-// + 4.5 DMA pieces under 640 MFMA cycles; 256x256: 12 + 4 under 512), not the K-half split.
-template <int NJ> struct Geo {
-    static constexpr int TBN = WN3 * NJ * 32;
-    static constexpr int PLANE = (TBM3 + TBN) * RBH;           // 36 KB / 32 KB
-    static constexpr int SLOT = 2 * PLANE;                     // one K tile
-    static constexpr int BIAS0 = 2 * SLOT;                     // per wave 2 x 768 B: the bias of this tile and of the next one
-    static constexpr int LDS_BYTES = BIAS0 + 8 * 2 * 768;     // 159744 (the epilogue transposes through a free ring plane)
-    static constexpr int LOOKAHEAD = 4 + NJ;                   // DMA instructions of the last two phases may be in flight
-};
+// NJ3 = accumulator column tiles per wave: 5 -> the 256x320 tile.  NJ = 4 (a 256x256 tile with the same K-half schedule, incl.
+// the GEGLU pair epilogue below) was built and measured in round 3: it is 5-10 % SLOWER than igemm8.hip's X-row split on every
+// shape (profiles/archive/r03_igemm_tiles_bench_with_ksplit256.log: GEGLU L0 / L1 / L2 750 / 920 / 1039 against 833 / 1017 / 1141
+// TF/s) -- the 256x320 tile's advantage is its shape (load segment of 14 reads + 4.5 DMA pieces under 640 MFMA cycles; 256x256:
+// 12 + 4 under 512), not the K-half split.
+constexpr int NJ3 = 5;
+constexpr int TBN3 = WN3 * NJ3 * 32;                           // 320
+constexpr int PLANE = (TBM3 + TBN3) * RBH;                     // 36 KB
+constexpr int SLOT = 2 * PLANE;                                // one K tile
+constexpr int BIAS0 = 2 * SLOT;                                // per wave 2 x 768 B: the bias of this tile and of the next one
+constexpr int LDS_BYTES3 = BIAS0 + 8 * 2 * 768;                // 159744 (the epilogue transposes through a free ring plane)
+constexpr int LOOKAHEAD3 = 4 + NJ3;                            // DMA instructions of the last two phases may be in flight
 
 struct Cursor3 {                    // one K-half plane of the persistent K-tile stream
     int local;                      // walk position of the output tile it is in
@@ -70,11 +66,10 @@ struct Cursor3 {                    // one K-half plane of the persistent K-tile
 // whole tiles in the same persistent stream (the cursors prefetch it during the last whole tile's epilogue).
 // STATS: the epilogue also emits the GroupNorm pair sums of the outputs (mofa_igemm_args.stats); kinds 0 / 1 / 4 / 5, no
 // activation, no per-row vector (igemm320_stats_ok)
-template <int EPI, int NJ3, bool SPLIT = false, bool STATS = false>
+template <int EPI, bool SPLIT = false, bool STATS = false>
 __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_args a, const int tilesN, const int ntiles,
                                                               const Aux aux) {
     constexpr bool R1 = (EPI & EPI_R1) != 0, R2 = (EPI & EPI_R2) != 0, RV = (EPI & EPI_RV) != 0, GEGLU = (EPI & EPI_GEGLU) != 0;
-    constexpr int TBN3 = Geo<NJ3>::TBN, PLANE = Geo<NJ3>::PLANE, SLOT = Geo<NJ3>::SLOT, LOOKAHEAD3 = Geo<NJ3>::LOOKAHEAD;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // the ONLY shared object
     TileWalk walk;
     walk.init(ntiles);
@@ -194,7 +189,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
         bglds16(rsx, c.xo1, c.ikc * 128, pl + (wave + 8) * 1024);
         bglds16(rsw, c.wo0, wk, pl + XPL + wave * 1024);
         bglds16(rsw, c.wo0 + wd1, wk, pl + XPL + (wave + 8) * 1024);
-        if (NJ3 == 5 && grp == p) bglds16(rsw, c.wo0 + wd2, wk, pl + XPL + (16 + (wave & 3)) * 1024);
+        if (grp == p) bglds16(rsw, c.wo0 + wd2, wk, pl + XPL + (16 + (wave & 3)) * 1024);
     };
     auto advance = [&](Cursor3& c, const int p) __attribute__((always_inline)) {
         ++c.ksw;
@@ -224,7 +219,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     // difference between the two, nor between bias and no bias -- its first reading, "bias costs 15 %", was the slower first
     // measurement after fresh allocations.)
     const auto rsb = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? (unsigned)a.N * 4u : 0u, 0x00020000);
-    char* bias_lds = smem + Geo<NJ3>::BIAS0 + wave * 1536;
+    char* bias_lds = smem + BIAS0 + wave * 1536;
     auto bias_prefetch = [&](int phase_, int local_, int slot) __attribute__((always_inline)) {
         if (phase_ != 0) return;                                   // (a split-K item starts from zero; past the end: nothing)
         int tile_, kb_, ke_;
@@ -306,8 +301,8 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     //      or 320 (wn = 1) of a 640-byte-aligned row: the pairs are (0,1) (2,3) + tile 4, or tile 0 + (1,2) (3,4), so that
     //      every pair starts on a 128-byte boundary -----------------------------------------------------------------------------
     auto epilogue_light = [&](auto ac, auto wnc, f32x16 (&acc)[MI3][NJ3], const int mw, const int nw, char* eb) __attribute__((always_inline)) {
-        constexpr int J0 = (NJ3 == 5 && decltype(wnc)::v) ? 1 : 0;   // first tile of the first pair
-        constexpr int JS = decltype(wnc)::v ? 0 : 4;                 // NJ = 5: the tile without a partner
+        constexpr int J0 = decltype(wnc)::v ? 1 : 0;   // first tile of the first pair
+        constexpr int JS = decltype(wnc)::v ? 0 : 4;                 // the tile without a partner
         const int lane_e = lane_now();                             // (lane-derived offsets are not kept live across the K loop)
         const int lane = lane_e, l31 = lane & 31, lh = lane >> 5;
         f16* out = (f16*)a.out;
@@ -340,7 +335,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
                     if (mr < a.M && n + 8 <= a.N) *(f16x8*)(out + (size_t)mr * a.ldo + n) = o;
                 }
             }
-            if constexpr (NJ3 == 5) {                              // the single tile: 32 columns per row
+            {                                                      // the single tile: 32 columns per row
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     f16x4 o;
@@ -369,10 +364,10 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     //      fp16, then `+`); with one residual and s1 == 1 (every residual add of the networks except the AlphaBlender mixes) the
     //      add is 4 v_pk_add_f16 per 8 outputs.  A ring of D residual pieces is in flight ahead of the transposes. --------------
     auto epilogue_res16 = [&](auto wnc, auto unit, f32x16 (&acc)[MI3][NJ3], const int mw, const int nw, char* eb) __attribute__((always_inline)) {
-        constexpr int J0 = (NJ3 == 5 && decltype(wnc)::v) ? 1 : 0;   // first tile of the first pair
-        constexpr int JS = decltype(wnc)::v ? 0 : 4;                 // NJ = 5: the tile without a partner
+        constexpr int J0 = decltype(wnc)::v ? 1 : 0;   // first tile of the first pair
+        constexpr int JS = decltype(wnc)::v ? 0 : 4;                 // the tile without a partner
         constexpr bool UNIT = decltype(unit)::v != 0;                // one residual, s1 == 1: packed fp16 adds
-        constexpr int PPI = NJ3 == 5 ? 10 : 8, NP = MI3 * PPI;       // store pieces (16 bytes per lane) per row tile / per tile
+        constexpr int PPI = 10, NP = MI3 * PPI;       // store pieces (16 bytes per lane) per row tile / per tile
         const int lane_e = lane_now();
         const int lane = lane_e, l31 = lane & 31, lh = lane >> 5;
         f16* out = (f16*)a.out;
@@ -447,7 +442,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
                     finish(i * PPI + pr * 4 + p, o);
                 }
             }
-            if constexpr (NJ3 == 5) {                              // the single tile: 32 columns per row
+            {                                                      // the single tile: 32 columns per row
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     f16x4 o;
@@ -492,7 +487,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
                 n = nw + 32 * JS + 8 * (lane & 3);
             }
         };
-        constexpr int D = STATS_D;
+        constexpr int D = 5;                                         // residual pieces in flight ahead of the transposes
         f16x8 L1[D];
         auto piece_loads = [&](int st, int slot) __attribute__((always_inline)) {
             int mr, n;
@@ -598,7 +593,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     };
     // ---- GEGLU pair kind: the weight rows are interleaved in blocks of 16 (weights.interleave_geglu), so accumulator tile j
     //      holds the value columns of outputs 16 j .. 16 j + 15 in registers 0-7 and the matching gate columns in registers
-    //      8-15 of the SAME lane: the product is lane-local and a wave's NJ tiles give 16 NJ output columns (80 of the tile's
+    //      8-15 of the SAME lane: the product is lane-local and a wave's NJ3 tiles give 16 NJ3 output columns (80 of the tile's
     //      160).  out = s_acc * val * gelu(s_acc * gate), erf GELU as x * Phi(x) (common.h).  Tiles 0-3 (64 output columns)
     //      go through one 32 x 64 fp16 transpose and whole 128-byte row pieces, tile 4 (16 columns) through a second one ------
     auto epilogue_geglu = [&](auto s1c, f32x16 (&acc)[MI3][NJ3], const int mw, const int nw, char* eb) __attribute__((always_inline)) {
@@ -639,7 +634,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
                 const int mr = mw + 32 * i + row, n = no0 + 8 * blk;
                 if (mr < a.M && n + 8 <= nout) *(f16x8*)(out + (size_t)mr * a.ldo + n) = o;
             }
-            if constexpr (NJ3 == 5) {                              // tile 4: 16 columns per row
+            {                                                      // tile 4: 16 columns per row
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
                     const int c8 = 2 * g + lh;
@@ -843,7 +838,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
                 epilogue_rows(IC<0>{}, acc, mw, nw, eb);           // a per-row vector (tile straddles a frame): fp32 row path
             } else {                                               // (a uniform row-vector row is already in the accumulators)
                 const bool unit = R1 && !R2 && a.s1 == 1.0f;
-                if (NJ3 == 4 || wn == 0) {
+                if (wn == 0) {
                     if (unit) epilogue_res16(IC<0>{}, IC<1>{}, acc, mw, nw, eb);
                     else epilogue_res16(IC<0>{}, IC<0>{}, acc, mw, nw, eb);
                 } else {
@@ -853,7 +848,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
             }
         } else if (RV && idx_u < 0) {
             epilogue_rows(IC<0>{}, acc, mw, nw, eb);
-        } else if (NJ3 == 4 || wn == 0) {
+        } else if (wn == 0) {
             if (RV || a.act == MOFA_ACT_NONE) epilogue_light(IC<MOFA_ACT_NONE>{}, IC<0>{}, acc, mw, nw, eb);
             else if (a.act == MOFA_ACT_SILU) epilogue_light(IC<MOFA_ACT_SILU>{}, IC<0>{}, acc, mw, nw, eb);
             else if (a.act == MOFA_ACT_RELU) epilogue_light(IC<MOFA_ACT_RELU>{}, IC<0>{}, acc, mw, nw, eb);
@@ -875,19 +870,19 @@ typedef void (*igemm320_kern_t)(const mofa_igemm_args, const int, const int, con
 // one thread per 8 output columns of a row; the slices are added in slice order (deterministic)
 __global__ __launch_bounds__(256) void igemm320_fixup_kernel(const mofa_igemm_args a, const float* __restrict__ ws, const int tile0,
                                                              const int nsplit, const int tilesN, const int R) {
-    constexpr int TBN = Geo<5>::TBN, PPR = TBN / 8, PPT = TBM3 * PPR;   // pieces per row / per tile
+    constexpr int PPR = TBN3 / 8, PPT = TBM3 * PPR;   // pieces per row / per tile
     const long long total = (long long)R * PPT;
     for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
         const int r = (int)(idx / PPT), rem = (int)(idx - (long long)r * PPT);
         const int rr = rem / PPR, pc = rem - rr * PPR;
         const int tile = tile0 + r, tm = tile / tilesN, tn = tile - tm * tilesN;
-        const int m = tm * TBM3 + rr, n = tn * TBN + pc * 8;
+        const int m = tm * TBM3 + rr, n = tn * TBN3 + pc * 8;
         if (m >= a.M || n + 8 > a.N) continue;
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = 0.f;
         for (int sl = 0; sl < nsplit; ++sl) {
-            const float* q = ws + ((size_t)(r * nsplit + sl) * TBM3 + rr) * TBN + pc * 8;
+            const float* q = ws + ((size_t)(r * nsplit + sl) * TBM3 + rr) * TBN3 + pc * 8;
             const f32x4 p0 = *(const f32x4*)q, p1 = *(const f32x4*)(q + 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[e] += p0[e]; v[4 + e] += p1[e]; }
@@ -936,10 +931,9 @@ __global__ __launch_bounds__(256) void igemm320_fixup_kernel(const mofa_igemm_ar
 // one thread per column pair, rows in order
 __global__ __launch_bounds__(192) void igemm320_tile_stats_kernel(const f16* __restrict__ out, const int ldo, float* __restrict__ stats,
                                                                   const int M, const int N, const int tile0, const int tilesN) {
-    constexpr int TBN = Geo<5>::TBN;
     const int tile = tile0 + (int)(blockIdx.x >> 2), tm = tile / tilesN, tn = tile - tm * tilesN;
-    const int m0 = tm * TBM3 + 64 * (int)(blockIdx.x & 3), n = tn * TBN + 2 * (int)threadIdx.x;
-    if (m0 >= M || (int)threadIdx.x >= TBN / 2 || n + 2 > N) return;
+    const int m0 = tm * TBM3 + 64 * (int)(blockIdx.x & 3), n = tn * TBN3 + 2 * (int)threadIdx.x;
+    if (m0 >= M || (int)threadIdx.x >= TBN3 / 2 || n + 2 > N) return;
     const f16x2 one2 = {(f16)1.0f, (f16)1.0f};
     float sm = 0.f, q = 0.f;
     const f16* p = out + (size_t)m0 * ldo + n;
@@ -958,45 +952,38 @@ __global__ __launch_bounds__(192) void igemm320_tile_stats_kernel(const f16* __r
 
 // (kind 7 = row vector + two residuals does not fit the register file beside 160 accumulators and occurs nowhere in the
 // model graph: it runs on the 4-wave tiles)
-static const igemm320_kern_t k_igemm320[9] = {igemm320_f16_kernel<0, 5>, igemm320_f16_kernel<1, 5>, igemm320_f16_kernel<2, 5>,
-                                               igemm320_f16_kernel<3, 5>, igemm320_f16_kernel<4, 5>, igemm320_f16_kernel<5, 5>,
-                                               igemm320_f16_kernel<6, 5>, nullptr, igemm320_f16_kernel<8, 5>};
+static const igemm320_kern_t k_igemm320[9] = {igemm320_f16_kernel<0>, igemm320_f16_kernel<1>, igemm320_f16_kernel<2>,
+                                               igemm320_f16_kernel<3>, igemm320_f16_kernel<4>, igemm320_f16_kernel<5>,
+                                               igemm320_f16_kernel<6>, nullptr, igemm320_f16_kernel<8>};
 static const igemm320_kern_t k_igemm320_split[7] = {
-    igemm320_f16_kernel<0, 5, true>, igemm320_f16_kernel<1, 5, true>, igemm320_f16_kernel<2, 5, true>, igemm320_f16_kernel<3, 5, true>,
-    igemm320_f16_kernel<4, 5, true>, igemm320_f16_kernel<5, 5, true>, igemm320_f16_kernel<6, 5, true>};
+    igemm320_f16_kernel<0, true>, igemm320_f16_kernel<1, true>, igemm320_f16_kernel<2, true>, igemm320_f16_kernel<3, true>,
+    igemm320_f16_kernel<4, true>, igemm320_f16_kernel<5, true>, igemm320_f16_kernel<6, true>};
 
 // STATS instantiations (GroupNorm pair sums from the epilogue): the kinds the networks' GroupNorm producers use -- plain (down-sampling
 // conv), one residual (conv2 / the temporal conv2 / proj_out), uniform row vector (conv1 + time embedding), both
-static const igemm320_kern_t k_igemm320_stats[7] = {igemm320_f16_kernel<0, 5, false, true>, igemm320_f16_kernel<1, 5, false, true>, nullptr,
-                                                     nullptr, igemm320_f16_kernel<4, 5, false, true>, igemm320_f16_kernel<5, 5, false, true>, nullptr};
-static const igemm320_kern_t k_igemm320_split_stats[7] = {igemm320_f16_kernel<0, 5, true, true>, igemm320_f16_kernel<1, 5, true, true>, nullptr,
-                                                           nullptr, igemm320_f16_kernel<4, 5, true, true>, igemm320_f16_kernel<5, 5, true, true>, nullptr};
+static const igemm320_kern_t k_igemm320_stats[7] = {igemm320_f16_kernel<0, false, true>, igemm320_f16_kernel<1, false, true>, nullptr,
+                                                     nullptr, igemm320_f16_kernel<4, false, true>, igemm320_f16_kernel<5, false, true>, nullptr};
+static const igemm320_kern_t k_igemm320_split_stats[7] = {igemm320_f16_kernel<0, true, true>, igemm320_f16_kernel<1, true, true>, nullptr,
+                                                           nullptr, igemm320_f16_kernel<4, true, true>, igemm320_f16_kernel<5, true, true>, nullptr};
 
 int igemm320_init() {
-    for (igemm320_kern_t k : k_igemm320)
-        if (k && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, Geo<5>::LDS_BYTES) != hipSuccess)
-            return MOFA_ELAUNCH;
-    for (igemm320_kern_t k : k_igemm320_split)
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, Geo<5>::LDS_BYTES) != hipSuccess)
-            return MOFA_ELAUNCH;
-    for (int i = 0; i < 7; ++i)
-        for (igemm320_kern_t k : {k_igemm320_stats[i], k_igemm320_split_stats[i]})
-            if (k && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, Geo<5>::LDS_BYTES) != hipSuccess)
-                return MOFA_ELAUNCH;
-    return MOFA_OK;
+    return mofa_lds_optin(k_igemm320, LDS_BYTES3) == MOFA_OK && mofa_lds_optin(k_igemm320_split, LDS_BYTES3) == MOFA_OK &&
+                   mofa_lds_optin(k_igemm320_stats, LDS_BYTES3) == MOFA_OK && mofa_lds_optin(k_igemm320_split_stats, LDS_BYTES3) == MOFA_OK
+               ? MOFA_OK
+               : MOFA_ELAUNCH;
 }
 
 // can a launch with these arguments emit mofa_igemm_args.stats?  (a->stats itself is not looked at)
 bool igemm320_stats_ok(const mofa_igemm_args* a) {
     if (!a || !a->x || !a->w || !a->out || a->M <= 0 || a->N <= 0 || a->Cin <= 0 || a->Cin % 64 != 0) return false;
     if (a->act != MOFA_ACT_NONE || a->r2 || (a->r1 && a->s1 != 1.0f)) return false;
-    if (a->M % 64 != 0 || a->N % Geo<5>::TBN != 0) return false;
+    if (a->M % 64 != 0 || a->N % TBN3 != 0) return false;
     if (a->rowvec && (a->rv_mod_in != 1 || a->rv_div <= 0 || a->rv_div % 64 != 0)) return false;   // constant over a wave's 64 rows
     if (a->tile != 0 && a->tile != MOFA_TILE_256X320) return false;
     const int taps = a->mode == MOFA_MODE_CONV3X3 ? (a->ksize > 0 ? a->ksize * a->ksize : 9) : (a->mode == MOFA_MODE_CONVT3 ? 3 : 1);
     const int kind = (a->r1 ? 1 : 0) | (a->rowvec ? 4 : 0);
     if (!igemm_pipe_eligible(a, kind, (long long)taps * a->Cin)) return false;
-    if ((long long)(a->N + Geo<5>::TBN) * taps * a->Cin * 2 >= 0x7ff00000LL) return false;
+    if ((long long)(a->N + TBN3) * taps * a->Cin * 2 >= 0x7ff00000LL) return false;
     return true;
 }
 
@@ -1018,7 +1005,7 @@ int igemm320_split(long long T, int nk, int n_cu, long long ws_bytes) {
     // dump and the fix-up launch (about 25 us; profiles/archive/r03b_kernel_stats_bench.md: splitting the shallow-K launches of the
     // clip -- 5 100 of 12 012 -- made it 4 % SLOWER)
     if (s >= 2 && 2.0 * nk * (1.0 - 1.0 / (double)s) < 50.0) s = 1;
-    const long long per = (long long)TBM3 * Geo<5>::TBN * 4;
+    const long long per = (long long)TBM3 * TBN3 * 4;
     while (s >= 2 && R * s * per > ws_bytes) --s;
     return s >= 2 ? (int)s : 1;
 }
@@ -1027,7 +1014,7 @@ int igemm320_split(long long T, int nk, int n_cu, long long ws_bytes) {
 int igemm320_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t stream) {
     const int taps = a->mode == MOFA_MODE_CONV3X3 ? (a->ksize > 0 ? a->ksize * a->ksize : 9) : (a->mode == MOFA_MODE_CONVT3 ? 3 : 1);
     if (kind == 7 || !igemm_pipe_eligible(a, kind, (long long)taps * a->Cin)) return 1;
-    constexpr int tbn = Geo<5>::TBN;
+    constexpr int tbn = TBN3;
     if ((long long)(a->N + tbn) * taps * a->Cin * 2 >= 0x7ff00000LL) return 1;   // unclamped W row offsets stay below W_DEAD
     const int tilesM = cdiv(a->M, TBM3), tilesN = cdiv(a->N, tbn);
     const long long nt = (long long)tilesM * tilesN;
@@ -1040,7 +1027,7 @@ int igemm320_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t st
     if (S == 1) {
         int grid = (int)(nt < n_cu ? ((nt + 7) / 8) * 8 : (n_cu / 8) * 8);
         if (grid < 8) grid = 8;
-        hipLaunchKernelGGL(a->stats ? k_igemm320_stats[kind] : k_igemm320[kind], dim3(grid), dim3(512), Geo<5>::LDS_BYTES, stream, *a, tilesN,
+        hipLaunchKernelGGL(a->stats ? k_igemm320_stats[kind] : k_igemm320[kind], dim3(grid), dim3(512), LDS_BYTES3, stream, *a, tilesN,
                            (int)nt, aux);
         MOFA_CHECK_LAUNCH();
         return MOFA_OK;
@@ -1055,7 +1042,7 @@ int igemm320_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t st
     aux.ws = (float*)a->workspace;
     int grid = full > 0 ? (n_cu / 8) * 8 : ((items + 7) / 8) * 8;
     if (grid < items) return MOFA_EINVAL;                       // (R * S <= n_cu by construction)
-    hipLaunchKernelGGL(a->stats ? k_igemm320_split_stats[kind] : k_igemm320_split[kind], dim3(grid), dim3(512), Geo<5>::LDS_BYTES, stream, *a,
+    hipLaunchKernelGGL(a->stats ? k_igemm320_split_stats[kind] : k_igemm320_split[kind], dim3(grid), dim3(512), LDS_BYTES3, stream, *a,
                        tilesN, (int)full, aux);
     MOFA_CHECK_LAUNCH();
     const long long pieces = (long long)R * TBM3 * (tbn / 8);

@@ -634,16 +634,9 @@ extern "C" int mofa_igemm8_set_probe(int var, void* trace) {
 #endif
 
 int igemm8_init() {
-    for (igemm8_kern_t k : k_igemm8)
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess)
-            return MOFA_ELAUNCH;
+    if (mofa_lds_optin(k_igemm8, LDS_BYTES) != MOFA_OK) return MOFA_ELAUNCH;
 #ifdef MOFA_PROBE
-    for (igemm8_kern_t k : k_probe_kern)
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess)
-            return MOFA_ELAUNCH;
-    for (igemm8_kern_t k : k_trace_kern)
-        if (k && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess)
-            return MOFA_ELAUNCH;
+    if (mofa_lds_optin(k_probe_kern, LDS_BYTES) != MOFA_OK || mofa_lds_optin(k_trace_kern, LDS_BYTES) != MOFA_OK) return MOFA_ELAUNCH;
 #endif
     return MOFA_OK;
 }

@@ -26,10 +26,7 @@ constexpr int LN_C = 320, LN_KS = 20, LN_CHUNK = 2 * LN_KS * 1024;       // 40 K
 constexpr int LN_OFF_T = 3 * LN_CHUNK;                                   // per wave 4 KB: a chunk's 32 rows x 64 columns, for the store transpose
 constexpr int LN_OFF_B = LN_OFF_T + 8 * 4096;                            // ring of three 1 KB bias pieces (a chunk's 64 floats first)
 constexpr int LN_LDS_BYTES = LN_OFF_B + 3 * 1024;                        // 158 720
-#ifndef LN_LOOK_D
-#define LN_LOOK_D 6
-#endif
-constexpr int LN_LOOK = LN_LOOK_D;                                        // fragment reads in flight ahead of the MFMA that consumes them
+constexpr int LN_LOOK = 6;                                                // fragment reads in flight ahead of the MFMA that consumes them
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -51,14 +48,9 @@ __device__ __forceinline__ void static_for(F&& f) {
 // two barriers per step -- is 5-20 % SLOWER than both waves in the same phase with one barrier.)
 // The counts are exact because every step issues exactly that: the stores are buffer stores (rows beyond M are dropped by the
 // descriptor's bounds check instead of being branched around), the pieces are always issued (beyond the last chunk they re-fetch).
-// (LIN_T_*: timing-only builds for tools/lin320_anatomy.sh -- wrong results, the data flow X -> MFMAs -> outputs stays alive)
 template <int K>
 __device__ __forceinline__ void lin_barrier() {
-#ifdef LIN_T_NOBAR
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(K) : "memory");
-#else
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(K) : "memory");
-#endif
 }
 
 template <bool NORM, bool RV, bool R1>
@@ -97,9 +89,6 @@ __global__ __launch_bounds__(512, 2) void lin320_kernel(const mofa_lin320_args a
     // the ring runs on a counter that does not restart at tile boundaries: chunk g (g = tile-local chunk + nchunk * tiles done)
     // lives in slot g % 3 and is fetched two steps ahead
     int g = 0;
-#ifdef LIN_T_NOEPI
-    float tkeep = 0.f;
-#endif
     const int my_tiles = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
     const int total = my_tiles * nchunk;
     dma_chunk(0, 0);
@@ -175,9 +164,7 @@ __global__ __launch_bounds__(512, 2) void lin320_kernel(const mofa_lin320_args a
                 int cn = c + 2;                                    //  last chunk they re-fetch a chunk nobody reads)
                 cn = cn >= nchunk ? cn - nchunk : cn;
                 cn = cn >= nchunk ? cn - nchunk : cn;             // (nchunk >= 1: c + 2 wraps at most twice)
-#ifndef LIN_T_NODMA
                 dma_chunk(cn, (g + 2) % 3);
-#endif
             }
             // bias (+ row vector) = the accumulators' first value; accumulator register r of tile t <-> column
             // 64 c + 32 t + 8 (r >> 2) + 4 lh + (r & 3): the bias piece is read from LDS (both k halves broadcast their 16 bytes)
@@ -216,10 +203,6 @@ __global__ __launch_bounds__(512, 2) void lin320_kernel(const mofa_lin320_args a
             // private to the wave ([row][8 segments of 16 bytes], segment index XOR (row & 7): conflict-free both ways) and leave as
             // whole 128-byte lines: lane j stores segment j % 8 of rows j / 8 + 8 i.
             char* ts = smem_ln + LN_OFF_T + wave * 4096;
-#ifdef LIN_T_NOEPI
-            tkeep += acc[0][0] + acc[1][0];                         // (the chunk's MFMAs stay alive; one store at the end of the kernel)
-            continue;
-#endif
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 f16x4 gq[4];
@@ -247,16 +230,10 @@ __global__ __launch_bounds__(512, 2) void lin320_kernel(const mofa_lin320_args a
                     for (int e = 0; e < 8; ++e) o[e] = (f16)((float)o[e] + s1 * (float)rp[i][e]);
                 }
                 // (a row beyond M lies beyond the descriptor's records: the store is issued and dropped)
-#ifdef LIN_T_NOSTORE
-                if (o[0] == (f16)12345.f)
-#endif
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rso, obyte + (unsigned)(8 * i) * ldo2 + 128u * (unsigned)c, 0, 0);
             }
         }
     }
-#ifdef LIN_T_NOEPI
-    if (tkeep == 12345.f) ((float*)a.out)[lane] = tkeep;
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -274,16 +251,13 @@ extern "C" int mofa_lin320_f16(const mofa_lin320_args* a, mofa_stream_t stream) 
     if (a->rowvec && (a->rv_div <= 0 || a->rv_mod_in <= 0 || a->rv_mod_out <= 0 || (((size_t)a->rowvec) & 15))) return MOFA_EINVAL;
     if (a->r1 && ((a->ldr1 & 7) || a->ldr1 < a->N || (((size_t)a->r1) & 15))) return MOFA_EINVAL;
     if (((long long)a->M + 256) * a->ldo * 2 >= 0xffffffffLL) return MOFA_EINVAL;   // outputs are addressed through a 32-bit buffer descriptor
+    if (a->reserved[0] || a->reserved[1] || a->reserved[2]) return MOFA_EINVAL;
     static const lin320_kern_t kerns[8] = {
         lin320_pick<false, false, false>(), lin320_pick<true, false, false>(), lin320_pick<false, true, false>(), lin320_pick<true, true, false>(),
         lin320_pick<false, false, true>(),  lin320_pick<true, false, true>(),  lin320_pick<false, true, true>(),  lin320_pick<true, true, true>()};
-    static const int n_cu = [] {
-        int dev = 0, cus = 0;
-        for (int i = 0; i < 8; ++i)
-            (void)hipFuncSetAttribute((const void*)kerns[i], hipFuncAttributeMaxDynamicSharedMemorySize, LN_LDS_BYTES);
-        return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-                cus > 0) ? cus : 256;
-    }();
+    static LaunchSetup setup;
+    const int n_cu = setup.cus([](int) { return mofa_lds_optin(kerns, LN_LDS_BYTES); });
+    if (n_cu == 0) return MOFA_ELAUNCH;
     const int ntiles = (a->M + 255) / 256;
     const int grid = ntiles < n_cu ? ntiles : n_cu;
     const lin320_kern_t k = kerns[(a->norm ? 1 : 0) | (a->rowvec ? 2 : 0) | (a->r1 ? 4 : 0)];

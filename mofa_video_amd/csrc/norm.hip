@@ -410,20 +410,21 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const f16* __restrict__ x
 // rows per workgroup of gn_apply: ONE round of resident workgroups -- (workgroups that fit the chip) / frames chunks per frame, at
 // least 16 rows each.  (Until r04b: about 64 K elements per workgroup, which at level 0 made 2 250 workgroups for 2 048 slots: a
 // second round one tenth full, 4.5 TB/s where the same kernel streams 5.2 TB/s on 4 500 or 1 150 workgroups.)
+// Returns 0 when the launch geometry of the current device cannot be queried.
 static int gn_apply_rows_per_wg(int HW, int C, int nframes, int total_entries) {
-    // launch geometry of this chip, taken ONCE: a function-local static with an initialiser is initialised thread-safely (C++11), so the
-    // virtual-rank threads of the tests / several host threads cannot race on it (round-4 advice); every GPU of a node is the same part
-    struct Chip { int cus, slots; };
-    static const Chip chip = [] {
-        int dev = 0, cus = 0, nb = 0;
-        if (!(hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-              cus > 0))
-            cus = 256;
+    // launch geometry of the current device, taken once per device (common.h): CU count x workgroups of this kernel per CU
+    static LaunchSetup setup;
+    static int wg_per_cu[MOFA_MAX_DEVICES];
+    int dev = 0;
+    const int n_cu_ = setup.cus([](int d) {
         // (4 KB of dynamic LDS: the occupancy of this kernel is bound by its 8 waves per SIMD, not by C * 8 bytes of LDS, up to C = 1280)
-        if (!(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)gn_apply_kernel, 256, 4096) == hipSuccess && nb > 0)) nb = 8;
-        return Chip{cus, cus * nb};
-    }();
-    const int slots = chip.slots, n_cu_ = chip.cus;
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)gn_apply_kernel, 256, 4096) != hipSuccess || nb <= 0) return MOFA_ELAUNCH;
+        wg_per_cu[d] = nb;
+        return MOFA_OK;
+    }, &dev);
+    if (n_cu_ == 0) return 0;
+    const int slots = n_cu_ * wg_per_cu[dev];
     // wide inputs (decoder concat buffers, C = 1920 / 2560) are bound by LDS instead: C * 8 B of scale / shift + 8.5 KB static of 160 KB
     const int by_lds = 163840 / (C * 8 + 8704);
     const int per_cu = slots / n_cu_;
@@ -444,6 +445,7 @@ extern "C" int mofa_gn_apply_f16(const void* x, const float* part, const float* 
         return MOFA_EINVAL;                                  // C <= 4096 as mofa_gn_partial_f16 (C * 8 B of dynamic + 8.5 KB static LDS)
     const int nparts = mofa_gn_nparts(HW, C);
     const int rpw = gn_apply_rows_per_wg(HW, C, nframes, frames_per_stat * nparts);
+    if (rpw == 0) return MOFA_ELAUNCH;
     const int chunks = cdiv(HW, rpw);
     hipLaunchKernelGGL(gn_apply_kernel, dim3(chunks, nframes), dim3(256), (size_t)C * 8, (hipStream_t)stream, (const f16*)x, part,
                        gamma, beta, (f16*)y, HW, C, ldx, ldy, frames_per_stat, frames_per_stat * nparts,
@@ -610,11 +612,9 @@ extern "C" int mofa_layernorm_f16(const void* x, const float* gamma, const float
         return MOFA_EINVAL;
     if (rowvec && (rv_div <= 0 || rv_mod <= 0)) return MOFA_EINVAL;
     const int CV = C / 8;
-    static const int n_cu = [] {
-        int dev = 0, cus = 0;
-        return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-                cus > 0) ? cus : 256;
-    }();
+    static LaunchSetup setup;
+    const int n_cu = setup.cus();
+    if (n_cu == 0) return MOFA_ELAUNCH;
     hipStream_t st = (hipStream_t)stream;
     if (CV <= 40 && CV % 8 == 0) launch_layernorm<5, 8>(x, gamma, beta, y, M, C, ldx, ldy, eps, rowvec, rv_div, rv_mod, n_cu, st);
     else if (CV <= 48) launch_layernorm<3, 16>(x, gamma, beta, y, M, C, ldx, ldy, eps, rowvec, rv_div, rv_mod, n_cu, st);

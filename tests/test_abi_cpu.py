@@ -91,6 +91,15 @@ def test_fused_level0_entry_points_validate_layout_without_gpu():
                 dict(r1=A + 8, ldr1=320), dict(r1=A, ldr1=324),
                 dict(M=1 << 22, N=960, ldo=960)):                      # (M + 256) * ldo * 2 bytes beyond the 32-bit output descriptor
         assert lin(**bad) == -22, bad
+    # include/mofa_hip.h: reserved[] must be 0 (lib.py's structs zero it)
+    for i in range(4):
+        r = [0] * 4
+        r[i] = 1
+        assert ff(reserved=(ctypes.c_int32 * 4)(*r)) == -22, i
+    for i in range(3):
+        r = [0] * 3
+        r[i] = 1
+        assert lin(reserved=(ctypes.c_int32 * 3)(*r)) == -22, i
     from mofa_video_amd import ops
     assert ops.lin320_fits(460800, 960) and ops.lin320_fits(2 * 97 * 9216, 960) and not ops.lin320_fits(1 << 22, 960)
 
