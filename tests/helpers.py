@@ -29,6 +29,71 @@ def rel_l2(a, b):
     return ((a - b).norm() / (b.norm() + 1e-12)).item()
 
 
+class FrameErrors:
+    """per-frame figures of a product tensor against its reference (``frame_errors``): ``rel[i]`` = rel-L2 of frame i,
+    ``maxabs[i]`` = max|out - ref| / max|ref| over frame i, ``worst_rel`` / ``worst_abs`` = the frame numbers (``f0 + i``) where
+    they peak, ``worst_elem`` = index of the largest |out - ref| of the whole tensor, ``tensor`` = the tensor-wide rel-L2"""
+
+    def __init__(self, rel, maxabs, f0, worst_elem, tensor):
+        self.rel, self.maxabs, self.f0, self.worst_elem, self.tensor = rel, maxabs, f0, worst_elem, tensor
+        self.worst_rel = f0 + max(range(len(rel)), key=lambda i: rel[i])
+        self.worst_abs = f0 + max(range(len(maxabs)), key=lambda i: maxabs[i])
+
+    def frame(self, f):
+        """(rel-L2, max-abs ratio) of frame ``f`` (a frame number, f0 counted)"""
+        return self.rel[f - self.f0], self.maxabs[f - self.f0]
+
+    def summary(self):
+        return (f"tensor rel-L2 {self.tensor:.3e}; per frame rel-L2 max {max(self.rel):.3e} (frame {self.worst_rel}), "
+                f"max-abs / max|ref| max {max(self.maxabs):.3e} (frame {self.worst_abs}); worst element {self.worst_elem}")
+
+
+def frame_errors(out, ref, dim=1, f0=0):
+    """per-frame rel-L2 and max|delta| / max|ref| of ``out`` against ``ref`` along the frame axis ``dim`` (fp64, on the tensors'
+    device); frame numbers start at ``f0`` (the first frame of a shard).  Non-finite values give non-finite figures."""
+    assert tuple(out.shape) == tuple(ref.shape), (tuple(out.shape), tuple(ref.shape))
+    o = out.detach().to(ref.device, torch.float64).movedim(dim, 0)
+    r = ref.detach().to(torch.float64).movedim(dim, 0)
+    n = o.shape[0]
+    d = (o - r).reshape(n, -1)
+    r = r.reshape(n, -1)
+    rel = (d.norm(dim=1) / (r.norm(dim=1) + 1e-30)).tolist()
+    dabs = d.abs()
+    dabs = torch.where(torch.isnan(dabs), torch.full_like(dabs, math.inf), dabs)    # (a NaN is the worst element there is)
+    maxabs = (dabs.amax(dim=1) / (r.abs().amax(dim=1) + 1e-30)).tolist()
+    k = int(dabs.reshape(-1).argmax())
+    i, j = divmod(k, d.shape[1])                                                     # (frame, flat index inside the frame)
+    rest = list(out.shape)
+    del rest[dim]
+    idx = list(_unravel(j, rest))
+    idx.insert(dim, f0 + i)
+    tensor = float(d.norm() / (r.norm() + 1e-30))
+    return FrameErrors(rel, maxabs, f0, tuple(idx), tensor)
+
+
+def _unravel(j, shape):
+    idx = []
+    for s in reversed(shape):
+        j, m = divmod(j, s)
+        idx.append(m)
+    return reversed(idx)
+
+
+def check_frames(out, ref, rel_tol, abs_tol, dim=1, f0=0, what="", named=()):
+    """asserts rel-L2 < rel_tol and max|delta| / max|ref| < abs_tol for EVERY frame of ``out`` against ``ref`` (frame axis
+    ``dim``, frame numbers from ``f0``); prints the worst figures and those of the frames in ``named``; returns the FrameErrors.
+    The failure message names every frame out of bounds and the worst element."""
+    e = frame_errors(out, ref, dim, f0)
+    print(f"{what}: {e.summary()}")
+    for f in named:
+        r, a = e.frame(f)
+        print(f"{what}: frame {f}: rel-L2 {r:.3e}, max-abs / max|ref| {a:.3e}")
+    bad = [(f0 + i, r, a) for i, (r, a) in enumerate(zip(e.rel, e.maxabs)) if not (r < rel_tol and a < abs_tol)]
+    assert not bad, (f"{what}: " + "; ".join(f"frame {f} rel-L2 {r:.3e}, max-abs / max|ref| {a:.3e}" for f, r, a in bad) +
+                     f" (bars {rel_tol:g} / {abs_tol:g}); worst element {e.worst_elem}")
+    return e
+
+
 def oracle_models(cfg=None, seed=0, vae_cfg=None, cn_cfg=None):
     """returns (oracle_unet, oracle_controlnet, oracle_vae, sd_unet, sd_ctrl, sd_vae) with fp16-valued weights"""
     from oracle.controlnet import FlowControlNet

@@ -30,6 +30,7 @@ import pytest
 import torch
 
 import bench
+from helpers import check_frames
 from test_fullgeom_gpu import DEV, exact_fp32_gpu, gpu_oracle
 
 pytestmark = pytest.mark.gpu
@@ -39,6 +40,20 @@ LONG_FRAMES = int(os.environ.get("MOFA_FULLLOOP_LONG_FRAMES", "49"))
 LONG_STEPS = int(os.environ.get("MOFA_FULLLOOP_LONG_STEPS", "8"))
 W8_STEPS = min(int(os.environ.get("MOFA_FULLLOOP_W8_STEPS", "10")), STEPS)   # opt-in: 25 (profiles/r06_fullloop_full_steps.log)
 TOL = 2e-2
+# per-frame max|delta| / max|ref| of the sharded / windowed runs vs the oracle, about 3x the worst value measured on one MI355X at the
+# default step counts (per-frame rel-L2 is bounded by TOL): world 8 (10 steps) 5.3e-4 (rel-L2 5.6e-4); config 4 on 8 ranks (25 steps)
+# 5.6e-4 (rel-L2 4.2e-4); config 5 windows over 8 / 4 ranks (97 frames, 2 steps) 1.10e-3 at frame 93 (rel-L2 9.9e-4 at frame 95,
+# overlap-averaged frames 6e-4 .. 8e-4)
+W8_ABS, C4_ABS, C5_ABS = 1.6e-3, 1.7e-3, 3.3e-3
+
+
+def check_shard(keep, trace, steps, out, lay, edges, name, abs_tol):
+    """every frame of a rank's shard after every marked step (its first and last frame by name), and every frame of the gathered
+    clip (the first and last frame of every shard by name), against the oracle: rel-L2 < TOL and max-abs < abs_tol"""
+    for s in marks(steps):
+        check_frames(keep[s], trace[s - 1][:, lay.f0:lay.f1], TOL, abs_tol, f0=lay.f0, what=f"{name} after step {s}",
+                     named=(lay.f0, lay.f1 - 1))
+    check_frames(out, trace[-1], TOL, abs_tol, what=f"{name}: gathered clip", named=edges)
 
 
 def rel(a, b):
@@ -249,7 +264,8 @@ def test_config5_window_loop_hybrid_control_vs_oracle(world):
 
 def test_world8_baseline_layout_10_steps_vs_oracle(world):
     """config 2 on 8 virtual ranks: 2-way CFG x 4 frame shards (7 / 6 / 6 / 6 frames), ``W8_STEPS`` steps against the oracle's
-    plain loop (MOFA-Video-Traj/pipeline/pipeline.py:447-511)"""
+    plain loop (MOFA-Video-Traj/pipeline/pipeline.py:447-511); every frame of every shard after every marked step and of the
+    gathered clip within rel-L2 TOL and max-abs W8_ABS = 1.6e-3 (measured at 10 steps: rel-L2 <= 5.6e-4, max-abs <= 5.3e-4)"""
     from mofa_video_amd.parallel import FrameParallel, Layout, ThreadComm, ThreadWorld
     from mofa_video_amd.pipeline import FlowControlNetPipeline
     from mofa_video_amd.scheduler import EulerDiscreteScheduler
@@ -285,6 +301,7 @@ def test_world8_baseline_layout_10_steps_vs_oracle(world):
     assert not errors, errors
     x0 = _x0(inp["latents"], steps)
     worst, sizes = 0.0, []
+    edges = sorted({f for r in range(nranks) for f in (Layout(nranks, r, T).f0, Layout(nranks, r, T).f1 - 1)})
     for r in range(nranks):
         lay = Layout(nranks, r, T)
         sizes.append(lay.f1 - lay.f0)
@@ -292,6 +309,7 @@ def test_world8_baseline_layout_10_steps_vs_oracle(world):
                            slice(lay.f0, lay.f1))
         e_all = rel(outs[r], trace[-1])
         print(f"world {nranks} rank {r}: gathered clip after {steps} steps rel-L2 {e_all:.3e} vs oracle")
+        check_shard(keeps[r], trace, steps, outs[r], lay, edges, f"world {nranks} rank {r}", W8_ABS)
         worst = max(worst, e_all, *errs.values(), *upd.values())
     assert sizes[:4] == [7, 6, 6, 6], sizes
     assert worst < TOL, worst
@@ -323,7 +341,8 @@ def _virtual_ranks(nranks, fn):
 def test_config4_hybrid_frames_sharded_over_8_ranks_vs_oracle(world):
     """BASELINE config 4 as it is worded: the Hybrid dual-adapter clip with its frames sharded over 8 ranks (2-way CFG x 4 frame
     shards of 7 / 6 / 6 / 6; both adapters warp and step only the rank's frames, the mask blend is per frame), all ``STEPS`` steps,
-    every rank's shard after the marked steps and the gathered clip against the oracle's Hybrid loop"""
+    every rank's shard after the marked steps and the gathered clip against the oracle's Hybrid loop; every frame within rel-L2 TOL
+    and max-abs C4_ABS = 1.7e-3 (measured: rel-L2 <= 4.2e-4, max-abs <= 5.6e-4)"""
     from mofa_video_amd.parallel import FrameParallel, Layout, ThreadComm
     from mofa_video_amd.pipeline import HybridFlowControlNetPipeline
     from mofa_video_amd.scheduler import EulerDiscreteScheduler
@@ -344,12 +363,14 @@ def test_config4_hybrid_frames_sharded_over_8_ranks_vs_oracle(world):
     outs = _virtual_ranks(nranks, run)
     x0 = _x0(inp["latents"], STEPS)
     worst = 0.0
+    edges = sorted({f for r in range(nranks) for f in (Layout(nranks, r, T).f0, Layout(nranks, r, T).f1 - 1)})
     for r in range(nranks):
         lay = Layout(nranks, r, T)
         errs, upd = report(f"config 4 (Hybrid), world {nranks} rank {r} (half {lay.half}, frames {lay.f0}..{lay.f1 - 1})", keeps[r], trace,
                            x0, STEPS, slice(lay.f0, lay.f1))
         e_all = rel(outs[r], trace[-1])
         print(f"config 4 (Hybrid), world {nranks} rank {r}: gathered clip after {STEPS} steps rel-L2 {e_all:.3e} vs oracle")
+        check_shard(keeps[r], trace, STEPS, outs[r], lay, edges, f"config 4 (Hybrid), world {nranks} rank {r}", C4_ABS)
         worst = max(worst, e_all, *errs.values(), *upd.values())
     assert worst < TOL, worst
 
@@ -358,7 +379,8 @@ def test_config5_full_length_97_frames_single_gpu_and_8_ranks_vs_oracle(world):
     """BASELINE config 5 at its full length: 97 frames = 7 distinct windows of 25 (stride 12) + the repeated last view, hybrid
     control in every window, 576x1024, full width, ``FULL_STEPS`` steps -- on one GPU, and with the windows dealt to 8 and to 4
     ranks (``parallel.WindowParallel``; 4 ranks = two rounds: the decode of finished chunks overlaps the second round of the last
-    step on a second stream), latents and the first / last decoded chunks against the oracle"""
+    step on a second stream), latents and the first / last decoded chunks against the oracle; the merged latents of every rank after
+    every step frame by frame within rel-L2 TOL and max-abs C5_ABS = 3.3e-3 (measured: rel-L2 <= 9.9e-4, max-abs <= 1.10e-3)"""
     from mofa_video_amd.parallel import ThreadComm, WindowParallel
     from mofa_video_amd.pipeline import KeypointFlowControlNetPipeline, window_views
     from mofa_video_amd.scheduler import EulerDiscreteScheduler
@@ -396,11 +418,19 @@ def test_config5_full_length_97_frames_single_gpu_and_8_ranks_vs_oracle(world):
     assert max(errs.values()) < TOL and max(upd.values()) < TOL and ef < TOL, (errs, max(upd.values()), ef)
     del frames
     # windows dealt to 8 ranks (the BASELINE layout: one round, one rank idle in the loop) and to 4 (two rounds, overlapped decode)
+    # frames in the overlap of two windows (the merge averages them) and the first / last frame of every window, by name
+    ov = [f for f in range(N) if sum((0 if i == 0 else t0) <= f < t1 for i, (t0, t1) in enumerate(views)) > 1]
+    named = sorted(set(ov) | {f for t0, t1 in views for f in (t0, t1 - 1)})
     for nranks in (8, 4):
-        lat = _virtual_ranks(nranks, lambda r, tw: run(WindowParallel(ThreadComm(tw, r), r, nranks), "latent"))
+        keeps = [dict() for _ in range(nranks)]
+        lat = _virtual_ranks(nranks, lambda r, tw: run(WindowParallel(ThreadComm(tw, r), r, nranks), "latent", keeps[r]))
         e_lat = max(rel(o, trace[-1]) for o in lat)
         assert all(torch.equal(o, lat[0]) for o in lat), "ranks disagree on the merged latents"
-        del lat
+        for r in range(nranks):
+            for s in marks(steps):
+                check_frames(keeps[r][s], trace[s - 1], TOL, C5_ABS, what=f"config 5, windows over {nranks} ranks, rank {r}, "
+                             f"merged latents after step {s}", named=named if r == 0 else ())
+        del lat, keeps
         chunks = _virtual_ranks(nranks, lambda r, tw: run(WindowParallel(ThreadComm(tw, r), r, nranks), "raw"))
         owner, ef = {}, 0.0
         for r, mine in enumerate(chunks):

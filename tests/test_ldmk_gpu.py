@@ -4,12 +4,16 @@ Stated fp16 tolerance: rel-L2 <= 1e-2 per forward tensor, <= 2e-2 for latents af
 import pytest
 import torch
 
-from helpers import LDMK_CN, LDMK_UNET, rel_l2, synthetic_inputs, synthetic_landmarks
+from helpers import LDMK_CN, LDMK_UNET, check_frames, rel_l2, synthetic_inputs, synthetic_landmarks
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 H = W = 256
 CROSS = LDMK_CN["cross_attention_dim"]
+# frame-sharded vs single rank, every frame (helpers.check_frames): rel-L2 < 2e-3 and max|delta| / max|ref| < SHARD_ABS.  Measured on
+# one MI355X: world 2 bit-identical; world 4 per-frame rel-L2 <= 9.6e-4, max-abs <= 1.17e-3 (spread evenly over the frames: the
+# tensor-wide figures are 9.0e-4 .. 9.3e-4).  SHARD_ABS = 3x the worst.
+SHARD_ABS = 3.5e-3
 
 
 @pytest.fixture(scope="module")
@@ -133,7 +137,8 @@ def test_keypoint_window_loop(models):
 @pytest.mark.parametrize("world", [2, 4])
 def test_hybrid_pipeline_frame_sharded_equals_single_rank(models, world):
     """Hybrid (two adapters + mask blend) on virtual ranks of this GPU: 2-way CFG x frame shards must reproduce the
-    single-rank latents (only the GroupNorm summation order differs)."""
+    single-rank latents (only the GroupNorm summation order differs), every frame within rel-L2 2e-3 and max-abs SHARD_ABS = 3.5e-3
+    (measured: world 2 bit-identical; world 4 per frame at most 9.5e-4 rel-L2, 1.05e-3 max-abs)."""
     import threading
 
     from mofa_video_amd.parallel import FrameParallel, Layout, ThreadComm, ThreadWorld
@@ -176,6 +181,7 @@ def test_hybrid_pipeline_frame_sharded_equals_single_rank(models, world):
         e = rel_l2(o, ref)
         print(f"hybrid world {world} rank {r}: latents rel-L2 vs single rank {e:.3e}")
         assert tuple(o.shape) == tuple(ref.shape) and e < 2e-3, (r, e)
+        check_frames(o, ref, 2e-3, SHARD_ABS, what=f"hybrid world {world} rank {r} vs single rank")
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -223,7 +229,8 @@ def test_keypoint_loop_window_parallel_equals_single_rank(models, world):
 def test_keypoint_single_window_frame_sharded_equals_single_rank(models, world, hybrid):
     """BASELINE config 3 is ONE window that is the whole clip (num_frames == window_size): with a parallel.FrameParallel the
     Keypoint pipeline frame-shards it (2-way CFG x frame shards) like the Traj / Hybrid pipelines -- it must reproduce the
-    single-rank window loop (whose two identical views average to the stepped window)."""
+    single-rank window loop (whose two identical views average to the stepped window), every frame within rel-L2 2e-3 and max-abs
+    SHARD_ABS = 3.5e-3 (measured: world 2 bit-identical; world 4 per frame at most 9.6e-4 rel-L2, 1.17e-3 max-abs)."""
     import threading
 
     from mofa_video_amd.parallel import FrameParallel, Layout, ThreadComm, ThreadWorld
@@ -268,6 +275,7 @@ def test_keypoint_single_window_frame_sharded_equals_single_rank(models, world, 
         e = rel_l2(o, ref)
         print(f"keypoint single window (hybrid={hybrid}) world {world} rank {r}: latents rel-L2 vs single rank {e:.3e}")
         assert tuple(o.shape) == tuple(ref.shape) and e < 2e-3, (r, e)
+        check_frames(o, ref, 2e-3, SHARD_ABS, what=f"keypoint single window (hybrid={hybrid}) world {world} rank {r} vs single rank")
     # a Layout built for another window size is refused (several windows: tests/test_pipeline_api_gpu.py)
     with pytest.raises(ValueError):
         run(FrameParallel(Layout(1, 0, T), ThreadComm(ThreadWorld(1), 0)), frames=T, window=T - 1)
