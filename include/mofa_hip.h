@@ -323,6 +323,45 @@ int mofa_softsplat_scatter_f32(const float* in, const float* flow, float* out_su
 int mofa_softsplat_weight_f32(const float* in, const float* metric, float* out, int N, int C, int H, int W, int mode,
                               mofa_stream_t stream);
 int mofa_softsplat_normalize_f32(const float* summed, float* out, int N, int C, int H, int W, int eps_mode, mofa_stream_t stream);
+/* Backward of the warp (softsplat_func.backward, models/softsplat.py:349-524, through the wrapper's mode prep and normalisation
+ * :243-270), fp32 NCHW, no atomics: every sum runs in a fixed order, so the gradients are reproducible bit for bit.  Element
+ * offsets are 64-bit; H * W must stay below 2^29 and N at most 65535 (MOFA_EINVAL otherwise).
+ *   mofa_softsplat_norm_f32: norm fp32 [N][H][W] = the per-target sum of splat weights of flow [N][2][H][W], added in the order
+ *     mofa_softsplat_avg_f16 adds them, so norm + 1e-7 is bit for bit what its 'avg' forward divided by.  ws: the CSR workspace,
+ *     mofa_softsplat_ws_bytes(N, H, W) bytes.
+ *   mofa_softsplat_grad_prologue_f32: per target of the normalised modes, with S = norm (the splatted last channel), nu = n(S) as
+ *     mofa_softsplat_normalize_f32's eps_mode forms it, grad / out the fp32 [N][C][H][W] gradient and value of the normalised
+ *     output:  inv = 1 / nu,  glast = -n'(S) * sum_c grad_c * out_c / nu  (both fp32 [N][H][W]; n' = 0 where 'zeroeps' replaced a
+ *     zero or 'clipeps' clamped, 1 otherwise).
+ *   mofa_softsplat_grad_f32: the gradients of one splat of Ĩ = prep(I, m), Ĩ with Cs channels:
+ *     prep 0  Ĩ = I              ('sum*' with inv = NULL; 'avg-<suffix>', whose normaliser is I's own last channel)  Cs = C
+ *     prep 1  Ĩ = [I | 1]        ('avg')                                                                           Cs = C + 1
+ *     prep 2  Ĩ = [I * m | m]    ('linear*')                                                                       Cs = C + 1
+ *     prep 3  Ĩ = [I e^m | e^m]  ('soft*')                                                                         Cs = C + 1
+ *     grad has Cg = Cs - 1 channels when inv / glast are given (the normalised modes: ghat_c = grad_c * inv for c < Cg, ghat_Cg =
+ *     glast), Cg = Cs without them (the raw sum: ghat = grad).  A source whose target is not finite gets 0 in every gradient.
+ *     Every output is optional (NULL = not computed; at least one); `in` is read only for grad_flow / grad_metric.  The channels
+ *     are split into `slices` (1 <= slices <= Cs) of ceil(Cs / slices) channels, one workgroup row each; with slices > 1 and
+ *     grad_flow or grad_metric, `partial` holds slices * N * 3 * H * W floats (the per-slice flow / metric sums, added in slice
+ *     order by a second launch).  The result depends on `slices`; for a given shape the caller keeps it fixed. */
+typedef struct mofa_softsplat_grad_args {
+    const float* grad;      /* fp32 [N][Cg][H][W]                               */
+    const float* flow;      /* fp32 [N][2][H][W]                                */
+    const float* in;        /* fp32 [N][C][H][W] (with grad_flow / grad_metric) */
+    const float* metric;    /* fp32 [N][H][W], prep 2 / 3 only                  */
+    const float* inv;       /* fp32 [N][H][W] or NULL (prologue)                */
+    const float* glast;     /* fp32 [N][H][W], with inv                         */
+    float* grad_in;         /* fp32 [N][C][H][W] or NULL                        */
+    float* grad_flow;       /* fp32 [N][2][H][W] or NULL                        */
+    float* grad_metric;     /* fp32 [N][H][W] or NULL, prep 2 / 3 only          */
+    float* partial;         /* fp32 [slices][N][3][H][W], see above             */
+    int32_t N, C, H, W, prep, slices;
+    int32_t reserved[4];    /* must be 0; sizeof(mofa_softsplat_grad_args) = 120 */
+} mofa_softsplat_grad_args;
+int mofa_softsplat_norm_f32(const float* flow, float* norm, void* ws, int N, int H, int W, mofa_stream_t stream);
+int mofa_softsplat_grad_prologue_f32(const float* grad, const float* out, const float* norm, float* inv, float* glast,
+                                     int N, int C, int H, int W, int eps_mode, mofa_stream_t stream);
+int mofa_softsplat_grad_f32(const mofa_softsplat_grad_args* a, mofa_stream_t stream);
 /* F.interpolate(flow, scale_factor=1/s) (nearest) / s  (svdxt_..._norefine.py:302-309): fp32 [n][2][H][W] -> [n][2][H/s][W/s] */
 int mofa_flow_downscale_f32(const float* flow, float* out, int n, int H, int W, int s, mofa_stream_t stream);
 

@@ -202,6 +202,19 @@ __global__ __launch_bounds__(256) void ss_gather_kernel(const f16* __restrict__ 
     }
 }
 
+// the per-flow CSR "target -> sorted (key, weight)" in ws (count, scan, fill, sort)
+static int ss_build_csr(const float* flow, void* ws, int nflows, int H, int W, hipStream_t st) {
+    const int HW = H * W;
+    const long long per = ws_ints_per_flow(HW);
+    if (hipMemsetAsync(ws, 0, (size_t)per * 4 * nflows, st) != hipSuccess) return MOFA_ELAUNCH;
+    dim3 gpix(cdiv(HW, 256), nflows);
+    hipLaunchKernelGGL(ss_count_kernel, gpix, dim3(256), 0, st, flow, (int*)ws, H, W, per);
+    hipLaunchKernelGGL(ss_scan_kernel, dim3(nflows), dim3(1024), 0, st, (int*)ws, HW, per);
+    hipLaunchKernelGGL(ss_fill_kernel, gpix, dim3(256), 0, st, flow, (int*)ws, H, W, per);
+    hipLaunchKernelGGL(ss_sort_kernel, gpix, dim3(256), 0, st, (int*)ws, HW, per);
+    return MOFA_OK;
+}
+
 extern "C" int mofa_softsplat_avg_f16(const void* feat, const float* flow, void* out, void* ws, int nflows, int H, int W,
                                       int C, int ldf, int ldo, mofa_stream_t stream) {
     if (!feat || !flow || !out || !ws || nflows <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || ldf % 8 != 0 ||
@@ -210,12 +223,7 @@ extern "C" int mofa_softsplat_avg_f16(const void* feat, const float* flow, void*
     const int HW = H * W;
     const long long per = ws_ints_per_flow(HW);
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws, 0, (size_t)per * 4 * nflows, st) != hipSuccess) return MOFA_ELAUNCH;
-    dim3 gpix(cdiv(HW, 256), nflows);
-    hipLaunchKernelGGL(ss_count_kernel, gpix, dim3(256), 0, st, flow, (int*)ws, H, W, per);
-    hipLaunchKernelGGL(ss_scan_kernel, dim3(nflows), dim3(1024), 0, st, (int*)ws, HW, per);
-    hipLaunchKernelGGL(ss_fill_kernel, gpix, dim3(256), 0, st, flow, (int*)ws, H, W, per);
-    hipLaunchKernelGGL(ss_sort_kernel, gpix, dim3(256), 0, st, (int*)ws, HW, per);
+    if (ss_build_csr(flow, ws, nflows, H, W, st) != MOFA_OK) return MOFA_ELAUNCH;
     hipLaunchKernelGGL(ss_gather_kernel, dim3(cdiv(HW, 4), nflows), dim3(256), 0, st, (const f16*)feat, (const int*)ws,
                        (f16*)out, HW, C, ldf, ldo, per);
     MOFA_CHECK_LAUNCH();
@@ -298,6 +306,242 @@ extern "C" int mofa_softsplat_normalize_f32(const float* summed, float* out, int
     long long nb = (total + 255) / 256;
     nb = nb > 16384 ? 16384 : nb;
     hipLaunchKernelGGL(splat_normalize_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, summed, out, C, HW, total, eps_mode);
+    MOFA_CHECK_LAUNCH();
+    return MOFA_OK;
+}
+
+// ---- backward: softsplat_func.backward (softsplat_ingrad :368-435, softsplat_flowgrad :439-524) through the wrapper's mode prep
+//      and normalisation (:243-270).  No atomics: every sum runs in a fixed order, so the gradients are reproducible bit for bit.
+//      Element offsets are 64-bit; one image plane must hold fewer than 2^29 pixels (the CSR keys corner * HW + source are int).
+
+// 'avg' normaliser before its + 1e-7: the per-target sum of splat weights in ss_gather_kernel's CSR order (bit-identical)
+__global__ void ss_norm_kernel(const int* __restrict__ ws, float* __restrict__ norm, int HW, long long per) {
+    const int i = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= HW) return;
+    const int* base = ws + per * i;
+    const int* offset = base + HW;
+    const float* wts = (const float*)(base + 3 * HW + 1 + 4 * HW);
+    const int a = offset[t], b = offset[t + 1];
+    float s = 0.f;
+    for (int j = a; j < b; ++j) s += wts[j];
+    norm[(size_t)i * HW + t] = s;
+}
+static bool ss_plane_ok(int H, int W) { return H > 0 && W > 0 && (int64_t)H * W < (1LL << 29); }
+
+extern "C" int mofa_softsplat_norm_f32(const float* flow, float* norm, void* ws, int N, int H, int W, mofa_stream_t stream) {
+    if (!flow || !norm || !ws || N <= 0 || N > 65535 || !ss_plane_ok(H, W)) return MOFA_EINVAL;
+    const int HW = H * W;
+    hipStream_t st = (hipStream_t)stream;
+    if (ss_build_csr(flow, ws, N, H, W, st) != MOFA_OK) return MOFA_ELAUNCH;
+    hipLaunchKernelGGL(ss_norm_kernel, dim3(cdiv(HW, 256), N), dim3(256), 0, st, (const int*)ws, norm, HW, ws_ints_per_flow(HW));
+    MOFA_CHECK_LAUNCH();
+    return MOFA_OK;
+}
+
+// per target: nu = n(norm) as splat_normalize_kernel forms it, inv = 1 / nu, glast = -n'(norm) * sum_c grad_c * out_c / nu.
+// 64 targets per block, the channels strided over the block's waves; the wave sums are added in wave order.
+#define SSG_PRO_WAVES 8
+__global__ __launch_bounds__(64 * SSG_PRO_WAVES) void ss_grad_prologue_kernel(const float* __restrict__ grad, const float* __restrict__ out,
+                                                                             const float* __restrict__ norm, float* __restrict__ inv,
+                                                                             float* __restrict__ glast, int C, int HW, int eps_mode) {
+    __shared__ float part[SSG_PRO_WAVES][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = blockIdx.y;
+    const int p = blockIdx.x * 64 + lane;
+    float dot = 0.f;
+    if (p < HW) {
+        const float* g = grad + (size_t)n * C * HW + p;
+        const float* o = out + (size_t)n * C * HW + p;
+        for (int c = wave; c < C; c += SSG_PRO_WAVES) dot = fmaf(g[(size_t)c * HW], o[(size_t)c * HW], dot);
+    }
+    part[wave][lane] = dot;
+    __syncthreads();
+    if (wave != 0 || p >= HW) return;
+    float d = part[0][lane];
+#pragma unroll
+    for (int w = 1; w < SSG_PRO_WAVES; ++w) d += part[w][lane];
+    const float s = norm[(size_t)n * HW + p];
+    float nu = s;
+    bool live = true;                         // n'(s) = 1; 0 where 'zeroeps' replaced a zero or 'clipeps' clamped
+    if (eps_mode == 0) nu = s + 0.0000001f;
+    else if (eps_mode == 1) { live = s != 0.0f; nu = live ? s : 1.0f; }
+    else if (eps_mode == 2) { live = s >= 0.0000001f; nu = fmaxf(s, 0.0000001f); }
+    const float r = 1.0f / nu;
+    inv[(size_t)n * HW + p] = r;
+    glast[(size_t)n * HW + p] = live ? -(d * r) : 0.0f;
+}
+
+extern "C" int mofa_softsplat_grad_prologue_f32(const float* grad, const float* out, const float* norm, float* inv, float* glast,
+                                                int N, int C, int H, int W, int eps_mode, mofa_stream_t stream) {
+    if (!grad || !out || !norm || !inv || !glast || N <= 0 || N > 65535 || C <= 0 || !ss_plane_ok(H, W) || eps_mode < 0 ||
+        eps_mode > 3)
+        return MOFA_EINVAL;
+    const int HW = H * W;
+    hipLaunchKernelGGL(ss_grad_prologue_kernel, dim3(cdiv(HW, 64), N), dim3(64 * SSG_PRO_WAVES), 0, (hipStream_t)stream, grad, out, norm,
+                       inv, glast, C, HW, eps_mode);
+    MOFA_CHECK_LAUNCH();
+    return MOFA_OK;
+}
+
+// splat_corners plus the weights' derivatives in x and y with the floor held fixed (softsplat_flowgrad :477-488)
+__device__ __forceinline__ bool splat_corners_grad(const float* __restrict__ flow, int s, int H, int W, Corners& c, float dx[4],
+                                                   float dy[4]) {
+    if (!splat_corners(flow, s, H, W, c)) return false;
+    const int y = s / W, x = s - y * W;
+    const float fx = (float)x + flow[s];
+    const float fy = (float)y + flow[H * W + s];
+    const float x0f = floorf(fx), y0f = floorf(fy);
+    const float x1f = (float)((int)x0f + 1), y1f = (float)((int)y0f + 1);
+    dx[0] = -(y1f - fy); dx[1] = y1f - fy; dx[2] = -(fy - y0f); dx[3] = fy - y0f;
+    dy[0] = -(x1f - fx); dy[1] = -(fx - x0f); dy[2] = x1f - fx; dy[3] = fx - x0f;
+    return true;
+}
+__device__ __forceinline__ bool ss_source_live(const float* __restrict__ flow, int s, int W, int HW) {
+    const int y = s / W, x = s - y * W;
+    return isfinite((float)x + flow[s]) && isfinite((float)y + flow[HW + s]);
+}
+// the mode prep's factor a: Ĩ = [I * a | a] ('avg': 1, 'linear': m, 'soft': e^m); 1 without prep
+__device__ __forceinline__ float ss_prep_factor(const float* __restrict__ metric, int prep, size_t i) {
+    return prep == 2 ? metric[i] : prep == 3 ? expf(metric[i]) : 1.0f;
+}
+__device__ __forceinline__ void ss_grad_store(const mofa_softsplat_grad_args& a, int n, int q, int HW, float sx, float sy, float sm) {
+    const bool live = ss_source_live(a.flow + (size_t)n * 2 * HW, q, a.W, HW);
+    const float f = live ? ss_prep_factor(a.metric, a.prep, (size_t)n * HW + q) : 0.0f;
+    if (a.grad_flow) {
+        a.grad_flow[((size_t)n * 2) * HW + q] = live ? f * sx : 0.0f;
+        a.grad_flow[((size_t)n * 2 + 1) * HW + q] = live ? f * sy : 0.0f;
+    }
+    if (a.grad_metric) a.grad_metric[(size_t)n * HW + q] = live ? (a.prep == 3 ? f * sm : sm) : 0.0f;
+}
+
+// One source pixel per lane, 64 per block, the splatted channels [c0, c1) of this block's slice strided over its waves.  Per
+// channel c: G_c = sum_k w_k ghat_c(t_k), D_c = sum_k dw_k ghat_c(t_k) (x and y), grad_in_c = a G_c; the flow / metric sums
+// sum_c Ĩ_c / a * (D_c, G_c) are added over the wave's channels in order, then over the waves in order (LDS), then -- with
+// slices > 1 -- over the slices in order by ss_grad_reduce_kernel.
+#define SSG_WAVES 4
+__global__ __launch_bounds__(64 * SSG_WAVES) void ss_grad_kernel(const mofa_softsplat_grad_args a, int chunk) {
+    __shared__ float red[3][SSG_WAVES][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int slice = blockIdx.y, n = blockIdx.z;
+    const int HW = a.H * a.W, C = a.C;
+    const int q = blockIdx.x * 64 + lane;
+    const bool normed = a.inv != nullptr;
+    const int Cs = C + (a.prep > 0);          // splatted channels
+    const int Cg = Cs - (normed ? 1 : 0);     // channels of grad; with normed, channel Cg is the normaliser
+    const bool sums = a.grad_flow || a.grad_metric;
+    const int c0 = slice * chunk, c1 = min(c0 + chunk, Cs);
+    float sx = 0.f, sy = 0.f, sm = 0.f;
+    if (q < HW) {
+        Corners cr;
+        float dx[4], dy[4];
+        const bool live = splat_corners_grad(a.flow + (size_t)n * 2 * HW, q, a.H, a.W, cr, dx, dy);
+        const float f = live ? ss_prep_factor(a.metric, a.prep, (size_t)n * HW + q) : 0.0f;
+        float cw[4], cx[4], cy[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!live) cr.t[k] = -1;
+            const float r = (normed && cr.t[k] >= 0) ? a.inv[(size_t)n * HW + cr.t[k]] : 1.0f;
+            cw[k] = cr.w[k] * r;
+            cx[k] = dx[k] * r;
+            cy[k] = dy[k] * r;
+        }
+        const float* g = a.grad + (size_t)n * Cg * HW;
+        const float* in = a.in + (size_t)n * C * HW + q;
+        float* gi = a.grad_in ? a.grad_in + (size_t)n * C * HW + q : nullptr;
+        for (int c = c0 + wave; c < min(c1, Cg); c += SSG_WAVES) {
+            const float* gc = g + (size_t)c * HW;
+            float G = 0.f, Dx = 0.f, Dy = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (cr.t[k] >= 0) {
+                    const float v = gc[cr.t[k]];
+                    G = fmaf(cw[k], v, G);
+                    Dx = fmaf(cx[k], v, Dx);
+                    Dy = fmaf(cy[k], v, Dy);
+                }
+            if (gi) gi[(size_t)c * HW] = f * G;
+            if (sums && live) {
+                const float v = in[(size_t)c * HW];
+                sx = fmaf(v, Dx, sx);
+                sy = fmaf(v, Dy, sy);
+                sm = fmaf(v, G, sm);
+            }
+        }
+        // the normaliser channel: ghat = glast at the corners, unscaled weights; Ĩ / a = I_Cg ('avg-<suffix>') or 1
+        if (normed && Cg >= c0 && Cg < c1 && (Cg - c0) % SSG_WAVES == wave) {
+            float G = 0.f, Dx = 0.f, Dy = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (cr.t[k] >= 0) {
+                    const float v = a.glast[(size_t)n * HW + cr.t[k]];
+                    G = fmaf(cr.w[k], v, G);
+                    Dx = fmaf(dx[k], v, Dx);
+                    Dy = fmaf(dy[k], v, Dy);
+                }
+            if (Cg < C && gi) gi[(size_t)Cg * HW] = f * G;
+            if (sums && live) {
+                const float v = Cg < C ? in[(size_t)Cg * HW] : 1.0f;
+                sx = fmaf(v, Dx, sx);
+                sy = fmaf(v, Dy, sy);
+                sm = fmaf(v, G, sm);
+            }
+        }
+    }
+    if (!sums) return;
+    red[0][wave][lane] = sx;
+    red[1][wave][lane] = sy;
+    red[2][wave][lane] = sm;
+    __syncthreads();
+    if (wave != 0 || q >= HW) return;
+#pragma unroll
+    for (int w = 1; w < SSG_WAVES; ++w) {
+        sx += red[0][w][lane];
+        sy += red[1][w][lane];
+        sm += red[2][w][lane];
+    }
+    if (gridDim.y == 1) {
+        ss_grad_store(a, n, q, HW, sx, sy, sm);
+    } else {
+        float* p = a.partial + (((size_t)slice * gridDim.z + n) * 3) * HW + q;
+        p[0] = sx;
+        p[HW] = sy;
+        p[2 * (size_t)HW] = sm;
+    }
+}
+
+__global__ __launch_bounds__(256) void ss_grad_reduce_kernel(const mofa_softsplat_grad_args a) {
+    const int HW = a.H * a.W, n = blockIdx.y;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= HW) return;
+    float sx = 0.f, sy = 0.f, sm = 0.f;
+    for (int s = 0; s < a.slices; ++s) {
+        const float* p = a.partial + (((size_t)s * a.N + n) * 3) * HW + q;
+        sx += p[0];
+        sy += p[HW];
+        sm += p[2 * (size_t)HW];
+    }
+    ss_grad_store(a, n, q, HW, sx, sy, sm);
+}
+
+extern "C" int mofa_softsplat_grad_f32(const mofa_softsplat_grad_args* a, mofa_stream_t stream) {
+    if (!a || !a->grad || !a->flow || a->N <= 0 || a->N > 65535 || a->C <= 0 || !ss_plane_ok(a->H, a->W) || a->prep < 0 || a->prep > 3)
+        return MOFA_EINVAL;
+    if (a->reserved[0] || a->reserved[1] || a->reserved[2] || a->reserved[3]) return MOFA_EINVAL;
+    const bool normed = a->inv != nullptr;
+    const int Cs = a->C + (a->prep > 0);
+    if (normed != (a->glast != nullptr) || (a->prep > 0 && !normed) || Cs - (normed ? 1 : 0) <= 0) return MOFA_EINVAL;
+    if ((a->prep >= 2) != (a->metric != nullptr) || (a->grad_metric && a->prep < 2)) return MOFA_EINVAL;
+    const bool sums = a->grad_flow || a->grad_metric;
+    if ((!a->grad_in && !sums) || (sums && !a->in) || a->slices < 1 || a->slices > Cs || a->slices > 65535 ||
+        (sums && a->slices > 1 && !a->partial))
+        return MOFA_EINVAL;
+    const int HW = a->H * a->W;
+    const int chunk = (Cs + a->slices - 1) / a->slices;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ss_grad_kernel, dim3(cdiv(HW, 64), a->slices, a->N), dim3(64 * SSG_WAVES), 0, st, *a, chunk);
+    if (sums && a->slices > 1)
+        hipLaunchKernelGGL(ss_grad_reduce_kernel, dim3(cdiv(HW, 256), a->N), dim3(256), 0, st, *a);
     MOFA_CHECK_LAUNCH();
     return MOFA_OK;
 }

@@ -60,6 +60,16 @@ class Lin320Args(C.Structure):
     ]
 
 
+class SoftsplatGradArgs(C.Structure):
+    _fields_ = [
+        ("grad", C.c_void_p), ("flow", C.c_void_p), ("inp", C.c_void_p), ("metric", C.c_void_p), ("inv", C.c_void_p),
+        ("glast", C.c_void_p), ("grad_in", C.c_void_p), ("grad_flow", C.c_void_p), ("grad_metric", C.c_void_p),
+        ("partial", C.c_void_p),
+        ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("prep", C.c_int32), ("slices", C.c_int32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
 # name -> argtypes (every symbol include/mofa_hip.h declares; tests check they all resolve)
@@ -105,6 +115,9 @@ PROTOTYPES = {
     "mofa_softsplat_scatter_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
     "mofa_softsplat_weight_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mofa_softsplat_normalize_f32": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "mofa_softsplat_norm_f32": [_P, _P, _P, _I, _I, _I, _P],
+    "mofa_softsplat_grad_prologue_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "mofa_softsplat_grad_f32": [_P, _P],            # (const mofa_softsplat_grad_args*: a byref(SoftsplatGradArgs), 120 bytes)
     "mofa_flow_downscale_f32": [_P, _P, _I, _I, _I, _I, _P],
     "mofa_prepare_model_input": [_P, _P, _P, _I, _I, _I, _F, _P],
     "mofa_cfg_euler_step": [_P, _P, _I, _I, _I, _F, _F, _F, _F, _P],

@@ -676,6 +676,70 @@ def softsplat_normalize_f32(summed, eps_mode):
     return out
 
 
+def softsplat_norm_f32(flow):
+    """flow fp32 [N,2,H,W] -> fp32 [N,H,W]: the per-target sum of splat weights, bit for bit the 'avg' forward's (before + 1e-7)"""
+    lib = L.load()
+    _chk(flow, F32)
+    N, _, H, W = flow.shape
+    ws = torch.empty((lib.mofa_softsplat_ws_bytes(N, H, W),), dtype=torch.uint8, device=flow.device)
+    norm = torch.empty((N, H, W), dtype=F32, device=flow.device)
+    L.check(lib.mofa_softsplat_norm_f32(L.ptr(flow.contiguous()), L.ptr(norm), L.ptr(ws), N, H, W, L.stream_ptr()),
+            "mofa_softsplat_norm_f32")
+    return norm
+
+
+def softsplat_grad_prologue_f32(grad, out, norm, eps_mode):
+    """grad / out fp32 [N,C,H,W] (gradient and value of the normalised output), norm fp32 [N,H,W] (the splatted last channel)
+    -> (1 / nu, glast), fp32 [N,H,W] each (include/mofa_hip.h)"""
+    lib = L.load()
+    _chk(grad, F32); _chk(out, F32); _chk(norm, F32)
+    N, Cc, H, W = out.shape
+    assert tuple(grad.shape) == (N, Cc, H, W) and norm.numel() == N * H * W
+    inv = torch.empty((N, H, W), dtype=F32, device=out.device)
+    glast = torch.empty_like(inv)
+    L.check(lib.mofa_softsplat_grad_prologue_f32(L.ptr(grad.contiguous()), L.ptr(out.contiguous()), L.ptr(norm.contiguous()), L.ptr(inv),
+                                                 L.ptr(glast), N, Cc, H, W, eps_mode, L.stream_ptr()), "mofa_softsplat_grad_prologue_f32")
+    return inv, glast
+
+
+def softsplat_grad_slices(N, Cs, HW):
+    """channel slices of mofa_softsplat_grad_f32 for a shape: about 1024 workgroups of 4 waves, at least 32 channels (8 per wave)
+    in a slice.  A function of the shape alone, so the gradients do not depend on which of them are requested."""
+    blocks = N * ((HW + 63) // 64)
+    return max(1, min((Cs + 31) // 32, (1024 + blocks - 1) // blocks))
+
+
+def softsplat_grad_f32(grad, flow, Cc, prep=0, tenIn=None, metric=None, inv=None, glast=None, want_in=True, want_flow=True,
+                       want_metric=False):
+    """gradients of one splat of prep(I, m) (include/mofa_hip.h, mofa_softsplat_grad_f32): grad fp32 [N,Cg,H,W], flow fp32
+    [N,2,H,W], tenIn fp32 [N,Cc,H,W] (for the flow / metric gradient), metric fp32 [N,1,H,W] (prep 2 / 3), inv / glast from
+    softsplat_grad_prologue_f32 (normalised modes) -> (dI [N,Cc,H,W], dF [N,2,H,W], dm [N,1,H,W]), None where not wanted"""
+    lib = L.load()
+    _chk(grad, F32); _chk(flow, F32)
+    N, _, H, W = flow.shape
+    HW = H * W
+    Cs = Cc + (1 if prep > 0 else 0)
+    assert tuple(grad.shape) == (N, Cs - (1 if inv is not None else 0), H, W), (tuple(grad.shape), Cc, prep)
+    dev = flow.device
+    sums = want_flow or want_metric
+    keep = [t.contiguous() if t is not None else None for t in (grad, flow, tenIn if sums else None, metric, inv, glast)]
+    for t in keep[2:]:
+        if t is not None:
+            _chk(t, F32)
+    dI = torch.empty((N, Cc, H, W), dtype=F32, device=dev) if want_in else None
+    dF = torch.empty((N, 2, H, W), dtype=F32, device=dev) if want_flow else None
+    dm = torch.empty((N, 1, H, W), dtype=F32, device=dev) if want_metric else None
+    slices = softsplat_grad_slices(N, Cs, HW)
+    part = torch.empty((slices, N, 3, HW), dtype=F32, device=dev) if sums and slices > 1 else None
+    a = L.SoftsplatGradArgs(*[L.ptr(t) for t in keep], L.ptr(dI), L.ptr(dF), L.ptr(dm), L.ptr(part), N, Cc, H, W, prep, slices)
+    t0 = TIMER.start() if TIMER is not None else None
+    L.check(lib.mofa_softsplat_grad_f32(C.byref(a), L.stream_ptr()), "mofa_softsplat_grad_f32")
+    if t0 is not None:       # grad once (the corner reads hit the cache), I and dI per wanted output, the per-pixel vectors
+        TIMER.stop("softsplat_grad", t0, nbytes=float(N) * HW * (4.0 * grad.shape[1] + (4.0 * Cc if want_in else 0.0)
+                                                                + (4.0 * Cc if sums else 0.0) + 32.0))
+    return dI, dF, dm
+
+
 def flow_downscale(flow, s):
     lib = L.load()
     _chk(flow, F32)
