@@ -2,7 +2,10 @@
 and the frame-sharded temporal block call, so that the *host logic* (the exchange protocol of parallel.FrameParallel, weight repacking into 128-column head slots, the key-padding mask column, quant_conv
 folded into conv_out, trailing-pad geometry, buffer views) can be exercised without a GPU in the ``-m "not gpu"`` suite.
 It is installed by monkeypatching inside tests/test_frontend_host_cpu.py and the worker processes of tests/test_parallel_gloo.py only; the product has no CPU path
-(mofa_video_amd/lib.py raises without libmofa_hip.so, and these functions are never importable from the package)."""
+(mofa_video_amd/lib.py raises without libmofa_hip.so, and these functions are never importable from the package).
+Every function here keeps the signature and the argument semantics of its entry point (``out=`` is written and returned, views
+at their own row stride, the documented roundings): tests/op_cases.py runs one case table through both sides
+(tests/test_op_contract_cpu.py here, tests/test_op_contract_gpu.py against the kernels)."""
 import torch
 import torch.nn.functional as F
 
@@ -12,7 +15,9 @@ F16, F32 = torch.float16, torch.float32
 
 
 def igemm(x, w, bias=None, geom=None, M=None, rowvec=None, rv=(1, 1, 1, 1 << 30), r1=None, s1=1.0, r2=None, s2=1.0,
-          act=L.ACT_NONE, s_acc=1.0, out=None, stats=False):
+          act=L.ACT_NONE, s_acc=1.0, out=None, tile=None, split_k=True, stats=False):
+    """tile / split_k / stats choose among kernels and launches that give the same result on the real side (each has GPU tests
+    of its own): ignored here"""
     from mofa_video_amd import ops
     geom = geom or ops.PLAIN
     N, Ktot = w.shape
@@ -57,6 +62,10 @@ def igemm(x, w, bias=None, geom=None, M=None, rowvec=None, rv=(1, 1, 1, 1 << 30)
         rows = torch.as_strided(rowvec, (int(idx.max()) + 1, N), (N, 1))
         y = y + rows.float()[idx]
     y = y * s_acc
+    if r1 is not None or r2 is not None:
+        # include/mofa_hip.h: WITH a residual the term s_acc * (...) is rounded to fp16 before the residuals are added in fp32
+        # (the reference's fp16 modules produce the layer's output in fp16 and then add); without one there is one rounding
+        y = y.to(F16).float()
     if r1 is not None:
         y = y + s1 * r1[:, :N].float()
     if r2 is not None:
@@ -88,7 +97,7 @@ def layer_norm(x, gamma, beta, eps=1e-5, rowvec=None, rv_div=1, rv_mod=1, out=No
         xf = xf + rowvec.float()[(m // rv_div) % rv_mod]
     y = F.layer_norm(xf, (x.shape[1],), gamma, beta, eps).to(F16)
     if out is not None:
-        out.copy_(y)
+        out[:, :x.shape[1]] = y                                 # (the kernel writes C columns at out's own row stride)
         return out
     return y
 
@@ -199,7 +208,7 @@ def group_norm(x, gamma, beta, nframes, HW, eps, frames_per_stat=1, silu=False, 
     y = F.silu(y) if silu else y
     y = y.permute(0, 2, 1).reshape(nframes * HW, C).to(F16)
     if out is not None:
-        out.copy_(y)
+        out[:, :C] = y                                          # (the kernel writes C columns at out's own row stride)
         return out
     return y
 
@@ -230,11 +239,21 @@ def gn_apply_gathered(x, part_all, count_per_group, gamma, beta, eps, out, nfram
     cpg = C // 32
     sc = rstd.float().repeat_interleave(cpg) * gamma
     y = x.float() * sc + (beta - mean.float().repeat_interleave(cpg) * sc)
-    out.copy_((F.silu(y) if silu else y).to(F16))
+    out[:, :C] = (F.silu(y) if silu else y).to(F16)
     return out
 
 
-def attn_spatial(q, k, v, nframes, heads, S, head_dim=64, scale=None, out=None, prescaled=False):
+def _into(out, y):
+    """what the entry points do with ``out=``: write the result's columns into the caller's buffer and return that buffer"""
+    if out is None:
+        return y
+    assert out.shape[0] == y.shape[0] and out.shape[1] >= y.shape[1] and out.dtype == y.dtype
+    out[:, :y.shape[1]] = y
+    return out
+
+
+def attn_spatial(q, k, v, nframes, heads, S, head_dim=64, scale=None, out=None, prescaled=False, query_blocks=0):
+    """query_blocks picks the workgroup height on the real side and leaves the result's meaning unchanged: ignored here"""
     assert head_dim in (64, 128) and S % 8 == 0
     scale = head_dim ** -0.5 if scale is None else scale
     if prescaled:                       # q holds Q * head_dim^-0.5 * log2(e): softmax in base 2
@@ -243,7 +262,7 @@ def attn_spatial(q, k, v, nframes, heads, S, head_dim=64, scale=None, out=None, 
     def split(t):
         return t.float().reshape(nframes, S, heads, head_dim).permute(0, 2, 1, 3)
     p = torch.softmax(split(q) @ split(k).transpose(-1, -2) * scale, dim=-1)
-    return (p @ split(v)).permute(0, 2, 1, 3).reshape(nframes * S, heads * head_dim).to(F16)
+    return _into(out, (p @ split(v)).permute(0, 2, 1, 3).reshape(nframes * S, heads * head_dim).to(F16))
 
 
 def attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=None, Tq=None, key_mask=None):
@@ -264,7 +283,7 @@ def attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=No
     if dead is not None:
         s = s.masked_fill(dead, float("-inf"))
     o = torch.softmax(s, dim=-1) @ vv
-    return o.permute(0, 3, 1, 2, 4).reshape(nclips * Tq * HW, C).to(F16)
+    return _into(out, o.permute(0, 3, 1, 2, 4).reshape(nclips * Tq * HW, C).to(F16))
 
 
 def timestep_embedding(t, dim):
@@ -305,8 +324,11 @@ def softmax_rows_(x):
 
 def nchw_to_tokens(x, ld=None, scale=1.0, out=None):
     n, C, H, W = x.shape
+    tok = (x * scale).permute(0, 2, 3, 1).reshape(-1, C).to(F16)
+    if out is not None:                                         # the C channels into an existing view; ld is not looked at
+        return _into(out, tok)
     y = torch.zeros((n * H * W, ld or C), dtype=F16)
-    y[:, :C] = (x * scale).permute(0, 2, 3, 1).reshape(-1, C).to(F16)
+    y[:, :C] = tok
     return y
 
 
@@ -340,12 +362,16 @@ def resize_bicubic_ac(x, Ho, Wo):
 
 
 def axpby_f32_(x, y, a=1.0, b=1.0):
-    y.copy_(a * x + b * y)
+    y.copy_(a * x if b == 0.0 else a * x + b * y)               # (b == 0 overwrites, as the kernel does: y may hold NaN)
     return y
 
 
-def cast_f16_to_f32(x):
-    return x.float()
+def cast_f16_to_f32(x, out=None):
+    if out is None:
+        return x.float()
+    assert out.is_contiguous() and out.numel() == x.numel() and out.dtype == F32
+    out.view(-1).copy_(x.reshape(-1))
+    return out
 
 
 def cast_f32_to_f16(x):

@@ -417,6 +417,114 @@ def test_scheduler_kernels_vs_oracle(ops):
     _close(latd, ref, tol=1e-5, what="cfg + euler")
 
 
+# the device-scalar forms every denoise step of the headline path calls (pipeline.py: prepare_model_input_dev, cfg_euler_step_dev_,
+# step_select as the first node of the captured step): the step's scalars come from a row of the per-clip table on the device
+def _step_table():
+    from mofa_video_amd.scheduler import EulerDiscreteScheduler
+    sch = EulerDiscreteScheduler()
+    sch.set_timesteps(25)
+    return torch.from_numpy(sch.step_table().copy())
+
+
+def _bits(t):
+    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def test_step_select_walks_the_table_and_clamps_at_the_last_row(ops):
+    tab_h = _step_table()
+    n = tab_h.shape[0]
+    assert tab_h.shape == (25, ops.STEP_SCALARS)
+    tab = tab_h.to(DEV)
+    cur_buf = torch.full((24,), float("nan"), device=DEV)                     # cur = words 8 .. 15 between guard words
+    cnt_buf = torch.tensor([0x5A5A5A5A, 0, 0x3C3C3C3C], dtype=torch.int32, device=DEV)
+    cur, counter = cur_buf[8:16], cnt_buf[1:2]
+    guard0 = cur_buf.clone()
+    for i in range(n + 2):
+        ops.step_select(tab, counter, cur)
+        row = min(i, n - 1)
+        assert torch.equal(_bits(cur).cpu(), _bits(tab_h[row])), f"call {i}: cur is not row {row}"
+        assert cnt_buf.tolist() == [0x5A5A5A5A, i + 1, 0x3C3C3C3C], (i, cnt_buf.tolist())
+        assert torch.equal(_bits(cur_buf[:8]), _bits(guard0[:8])) and torch.equal(_bits(cur_buf[16:]), _bits(guard0[16:])), f"call {i}"
+    assert torch.equal(_bits(tab.cpu()), _bits(tab_h))
+
+
+def _scheduler_case(T, h, w, seed=44):
+    """latents, image latents, and the network's prediction / the model input as views (ldn = 16 > 4, ldo = 24 > 8) into
+    NaN-filled guard buffers"""
+    g = torch.Generator().manual_seed(seed)
+    lat = torch.randn(T, 4, h, w, generator=g) * 50
+    img = torch.randn(2, 4, h, w, generator=g)
+    npred = torch.randn(2 * T * h * w, 4, generator=g).half()
+    M = 2 * T * h * w
+    np_buf = torch.full((M + 4, 16), float("nan"), dtype=torch.float16)
+    np_buf[2:2 + M, 4:8] = npred
+    return lat, img, npred, np_buf, M
+
+
+def _model_input(ops, lat, img, M, scal):
+    """-> (buffer, view [M, 16] at ldo = 24) written by the host-scalar form (scal a float) or the device-scalar form"""
+    buf = torch.full((M + 4, 24), float("nan"), dtype=torch.float16, device=DEV)
+    before = buf.clone()
+    view = buf[2:2 + M, 8:24]
+    if torch.is_tensor(scal):
+        ops.prepare_model_input_dev(lat.to(DEV), img.to(DEV), view, scal)
+    else:
+        ops.prepare_model_input(lat.to(DEV), img.to(DEV), view, scal)
+    keep = torch.ones(buf.shape, dtype=torch.bool, device=DEV)
+    keep[2:2 + M, 8:16] = False                                               # the 8 written columns of the view's rows
+    assert torch.equal(_bits(buf)[keep], _bits(before)[keep]), "model input: columns >= 8 or guard rows / columns were written"
+    assert torch.isfinite(view[:, :8]).all()
+    return view[:, :8].cpu()
+
+
+@pytest.mark.parametrize("T", [1, 5])
+def test_device_scalar_scheduler_kernels(ops, T):
+    """the device-scalar forms on rows of scheduler.step_table() (first, last -- sigma_next == 0 --, and two between) against
+    (a) the host-scalar forms given the same row's sigma / sigma_next as Python floats: latents bit-equal (same kernel, scalars
+    from another source), fp16 model input within 1 fp16 ulp (the host form computes 1 / sqrt(sigma^2 + 1) in the launcher, the
+    table carries it pre-computed by numpy), and (b) the oracle scheduler at the tolerances of test_scheduler_kernels_vs_oracle.
+    T = 1 takes the g = gmin branch of the guidance ramp."""
+    from oracle.scheduler import EulerDiscreteScheduler
+    h, w = 6, 8
+    tab_h = _step_table()
+    tab = tab_h.to(DEV)
+    n = tab_h.shape[0]
+    sch = EulerDiscreteScheduler()
+    sch.set_timesteps(n)
+    assert tab_h[n - 1, 1].item() == 0.0
+    lat, img, npred, np_buf, M = _scheduler_case(T, h, w)
+    for i in (0, 3, 12, n - 1):
+        sigma, sigma_next = tab_h[i, 0].item(), tab_h[i, 1].item()
+        assert abs(sigma - sch.sigmas[i].item()) <= 1e-6 * sigma and abs(sigma_next - sch.sigmas[i + 1].item()) <= 1e-6 * sigma
+        # model input
+        x_dev = _model_input(ops, lat, img, M, tab[i])
+        x_host = _model_input(ops, lat, img, M, sigma)
+        ulps = (_bits(x_dev[:, :4]).int() - _bits(x_host[:, :4]).int()).abs().max().item()
+        print(f"T={T} row {i}: model input, device-scalar vs host-scalar form: {ulps} fp16 ulp")
+        assert ulps <= 1, (i, ulps)
+        assert torch.equal(x_dev[:, 4:], x_host[:, 4:])
+        ref_lat = (lat / (sigma ** 2 + 1) ** 0.5).permute(0, 2, 3, 1).reshape(T * h * w, 4)
+        ref_img = img.permute(0, 2, 3, 1).reshape(2, h * w, 4)
+        for half in range(2):
+            blk = x_dev[half * T * h * w:(half + 1) * T * h * w]
+            _close(blk[:, :4], ref_lat, tol=1e-3, what=f"row {i}: model input latents (device scalars)")
+            _close(blk[:, 4:8].reshape(T, h * w, 4), ref_img[half].expand(T, -1, -1), tol=1e-3, what=f"row {i}: model input image")
+        # CFG + Euler
+        npd = np_buf.to(DEV)
+        np_before = npd.clone()
+        lat_dev, lat_host = lat.to(DEV).clone(), lat.to(DEV).clone()
+        ops.cfg_euler_step_dev_(lat_dev, npd[2:2 + M, 4:8], tab[i], 1.0, 3.0)
+        ops.cfg_euler_step_(lat_host, npd[2:2 + M, 4:8], sigma, sigma_next, 1.0, 3.0)
+        assert torch.equal(_bits(npd), _bits(np_before))
+        assert torch.equal(_bits(lat_dev), _bits(lat_host)), f"row {i}: device-scalar and host-scalar Euler steps differ"
+        sch._step_index = i
+        npf = npred.float().reshape(2, T, h, w, 4).permute(0, 1, 4, 2, 3)      # [2,T,4,h,w]
+        gs = (torch.linspace(1.0, 3.0, T) if T > 1 else torch.tensor([1.0])).view(T, 1, 1, 1)
+        v = npf[0] + gs * (npf[1] - npf[0])
+        _close(lat_dev, sch.step(v, sch.timesteps[i], lat), tol=1e-5, what=f"row {i}: cfg + euler (device scalars)")
+    assert torch.equal(_bits(tab.cpu()), _bits(tab_h))
+
+
 # ---------------------------------------------------------------------------------------------------------
 # kernels of the landmark / Hybrid / Keypoint paths
 # ---------------------------------------------------------------------------------------------------------
