@@ -362,6 +362,37 @@ int mofa_softsplat_norm_f32(const float* flow, float* norm, void* ws, int N, int
 int mofa_softsplat_grad_prologue_f32(const float* grad, const float* out, const float* norm, float* inv, float* glast,
                                      int N, int C, int H, int W, int eps_mode, mofa_stream_t stream);
 int mofa_softsplat_grad_f32(const mofa_softsplat_grad_args* a, mofa_stream_t stream);
+/* Forward of the warp in gather form, every mode of the wrapper (models/softsplat.py:232-274) in one call: fp32 NCHW in and out as
+ * the reference computes it (custom_fwd(cast_inputs=torch.float32)), the normalisation fused, no atomics on any value that reaches
+ * an output, so two calls on one input give the same bits.  One splat of Ĩ = prep(I, m), prep as in mofa_softsplat_grad_args:
+ *     strMode               prep  normalize  channels of out  normaliser S
+ *     'sum', 'sum-*'        0     0          C                -
+ *     'avg'                 1     1 (eps 0)  C                sum w
+ *     'avg-<suffix>'        0     1          C - 1            sum w * I_last   (the input's own last channel)
+ *     'linear*' / 'soft*'   2 / 3 1          C                sum w * m  /  sum w * e^m
+ *   in fp32 [N][C][H][W]; flow fp32 [N][2][H][W]; metric fp32 [N][H][W] with prep 2 / 3 and NULL otherwise; out fp32
+ *   [N][Co][H][W]; norm (optional, normalize = 1 only) fp32 [N][H][W] = S before its eps handling, what
+ *   mofa_softsplat_grad_prologue_f32 takes; ws the CSR workspace, mofa_softsplat_ws_bytes(N, H, W) bytes, rebuilt by every call.
+ *   Order of summation: per target the contributions are added in CSR order -- corners NW, NE, SW, SE, sources in raster order
+ *   within a corner -- as acc = acc + ((I * a) * w) with a = 1 / m / e^m, every product and every sum rounded on its own (no fused
+ *   multiply-add); with normalize = 1, out = acc / n(S), n as mofa_softsplat_normalize_f32's eps_mode forms it, a correctly rounded
+ *   division.  That is the order and the operation set of the CPU oracle: the raw sum equals it bit for bit.  A target with more
+ *   than 128 entries is summed by a whole workgroup, one channel per thread, in the same order.
+ *   The output channels are split into `slices` (1 <= slices <= Co) of ceil(Co / slices), one workgroup row each; every slice
+ *   forms the normaliser itself, so the result does not depend on `slices`.  Limits: N <= 65535, H * W < 2^29; prep >= 1 needs
+ *   normalize = 1; every rule is checked before any device call (MOFA_EINVAL).  No allocation, the caller's stream, no
+ *   synchronisation. */
+typedef struct mofa_softsplat_gather_args {
+    const float* in;        /* fp32 [N][C][H][W]                                 */
+    const float* flow;      /* fp32 [N][2][H][W]                                 */
+    const float* metric;    /* fp32 [N][H][W], prep 2 / 3 only                   */
+    float* out;             /* fp32 [N][Co][H][W]                                */
+    float* norm;            /* fp32 [N][H][W] or NULL                            */
+    void* ws;               /* mofa_softsplat_ws_bytes(N, H, W) bytes            */
+    int32_t N, C, H, W, prep, normalize, eps_mode, slices;
+    int32_t reserved[4];    /* must be 0; sizeof(mofa_softsplat_gather_args) = 96 */
+} mofa_softsplat_gather_args;
+int mofa_softsplat_gather_f32(const mofa_softsplat_gather_args* a, mofa_stream_t stream);
 /* F.interpolate(flow, scale_factor=1/s) (nearest) / s  (svdxt_..._norefine.py:302-309): fp32 [n][2][H][W] -> [n][2][H/s][W/s] */
 int mofa_flow_downscale_f32(const float* flow, float* out, int n, int H, int W, int s, mofa_stream_t stream);
 

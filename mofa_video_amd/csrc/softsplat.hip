@@ -203,7 +203,8 @@ __global__ __launch_bounds__(256) void ss_gather_kernel(const f16* __restrict__ 
 }
 
 // the per-flow CSR "target -> sorted (key, weight)" in ws (count, scan, fill, sort)
-static int ss_build_csr(const float* flow, void* ws, int nflows, int H, int W, hipStream_t st) {
+static void ss_launch_sort_wg(int* ws, const float* flow, int nflows, int H, int W, long long per, hipStream_t st);
+static int ss_build_csr(const float* flow, void* ws, int nflows, int H, int W, hipStream_t st, bool wg_sort = false) {
     const int HW = H * W;
     const long long per = ws_ints_per_flow(HW);
     if (hipMemsetAsync(ws, 0, (size_t)per * 4 * nflows, st) != hipSuccess) return MOFA_ELAUNCH;
@@ -211,7 +212,8 @@ static int ss_build_csr(const float* flow, void* ws, int nflows, int H, int W, h
     hipLaunchKernelGGL(ss_count_kernel, gpix, dim3(256), 0, st, flow, (int*)ws, H, W, per);
     hipLaunchKernelGGL(ss_scan_kernel, dim3(nflows), dim3(1024), 0, st, (int*)ws, HW, per);
     hipLaunchKernelGGL(ss_fill_kernel, gpix, dim3(256), 0, st, flow, (int*)ws, H, W, per);
-    hipLaunchKernelGGL(ss_sort_kernel, gpix, dim3(256), 0, st, (int*)ws, HW, per);
+    if (wg_sort) ss_launch_sort_wg((int*)ws, flow, nflows, H, W, per, st);
+    else hipLaunchKernelGGL(ss_sort_kernel, gpix, dim3(256), 0, st, (int*)ws, HW, per);
     return MOFA_OK;
 }
 
@@ -542,6 +544,246 @@ extern "C" int mofa_softsplat_grad_f32(const mofa_softsplat_grad_args* a, mofa_s
     hipLaunchKernelGGL(ss_grad_kernel, dim3(cdiv(HW, 64), a->slices, a->N), dim3(64 * SSG_WAVES), 0, st, *a, chunk);
     if (sums && a->slices > 1)
         hipLaunchKernelGGL(ss_grad_reduce_kernel, dim3(cdiv(HW, 256), a->N), dim3(256), 0, st, *a);
+    MOFA_CHECK_LAUNCH();
+    return MOFA_OK;
+}
+
+// ---- fp32 gather forward of every mode (mofa_softsplat_gather_f32): the splat of Ĩ = prep(I, m) as a per-target sum over the CSR,
+//      fp32 NCHW in and out, the normalisation fused, no atomics on a value.  Per target the contributions are added in CSR order
+//      (corners NW, NE, SW, SE; sources in raster order within a corner) as acc = acc + ((I * a) * w), every product and sum rounded
+//      on its own -- the CPU oracle's index_add_ order and operations, so the raw sum equals it bit for bit.
+#define SSF_WAVES 4
+#define SSF_REG 8        // CSR entries of its segment a lane keeps in registers; the rest it re-reads per channel
+#define SSF_LONG 128     // a longer segment is walked by the whole workgroup, one channel per thread
+
+// ss_sort_kernel for the gather forward: the same order, but a segment of more than SSF_LONG entries is not left to one thread
+// (a convergent flow puts up to 4 HW entries on a target: tens of milliseconds of serial heap sort).  Its keys are distinct
+// integers below 4 HW, so the workgroup marks them in a bitmap in LDS, and the set bits in ascending order ARE the sorted keys;
+// a key's position is the number of set bits below it, and its weight is recomputed from the flow (the same function that
+// ss_fill_kernel called: the same bits).  Nothing depends on the order in which ss_fill_kernel's atomics arrived.
+// Dynamic LDS: ceil(4 HW / 32) words; planes too large for it keep ss_sort_kernel (ss_wg_sort_fits).
+static inline int ss_bitmap_words(int HW) { return (int)((4LL * HW + 31) / 32); }
+static inline bool ss_wg_sort_fits(int HW) { return (ss_bitmap_words(HW) + 768) * 4LL <= 65536; }
+__global__ __launch_bounds__(256) void ss_sort_wg_kernel(const float* __restrict__ flow, int* __restrict__ ws, int H, int W,
+                                                         long long per, int words) {
+    extern __shared__ unsigned ss_bits[];
+    __shared__ int is_long[256];
+    __shared__ int part[256];
+    const int HW = H * W, i = blockIdx.y, tid = threadIdx.x;
+    const int t = blockIdx.x * 256 + tid;
+    int* base = ws + per * i;
+    const int* offset = base + HW;
+    int* keys = base + 3 * HW + 1;
+    float* wts = (float*)(base + 3 * HW + 1 + 4 * HW);
+    const float* fl = flow + (size_t)i * 2 * HW;
+    int a = 0, b = 0;
+    if (t < HW) {
+        a = offset[t];
+        b = offset[t + 1];
+    }
+    is_long[tid] = b - a > SSF_LONG;
+    if (b - a <= SS_INSERTION_MAX) {
+        for (int j = a + 1; j < b; ++j) {
+            const int kj = keys[j];
+            const float wj = wts[j];
+            int m = j - 1;
+            while (m >= a && keys[m] > kj) {
+                keys[m + 1] = keys[m];
+                wts[m + 1] = wts[m];
+                --m;
+            }
+            keys[m + 1] = kj;
+            wts[m + 1] = wj;
+        }
+    } else if (b - a <= SSF_LONG) {
+        int* k = keys + a;
+        float* w = wts + a;
+        const int n = b - a;
+        for (int r = n / 2 - 1; r >= 0; --r) ss_sift_down(k, w, r, n);
+        for (int end = n - 1; end > 0; --end) {
+            const int kt = k[0]; k[0] = k[end]; k[end] = kt;
+            const float wt = w[0]; w[0] = w[end]; w[end] = wt;
+            ss_sift_down(k, w, 0, end);
+        }
+    }
+    __syncthreads();
+    const int wpt = (words + 255) / 256;                       // bitmap words per thread, a contiguous run
+    const int w0 = min(tid * wpt, words), w1 = min(w0 + wpt, words);
+    for (int l = 0; l < 256; ++l) {
+        if (!is_long[l]) continue;                             // (uniform: LDS)
+        const int tl = blockIdx.x * 256 + l;
+        const int la = offset[tl], lb = offset[tl + 1];
+        for (int w = tid; w < words; w += 256) ss_bits[w] = 0u;
+        __syncthreads();
+        for (int j = la + tid; j < lb; j += 256) {
+            const int key = keys[j];
+            atomicOr(&ss_bits[key >> 5], 1u << (key & 31));
+        }
+        __syncthreads();
+        int mine = 0;
+        for (int w = w0; w < w1; ++w) mine += __popc(ss_bits[w]);
+        part[tid] = mine;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {
+            const int v = tid >= o ? part[tid - o] : 0;
+            __syncthreads();
+            part[tid] += v;
+            __syncthreads();
+        }
+        int pos = la + part[tid] - mine;
+        for (int w = w0; w < w1; ++w) {
+            unsigned word = ss_bits[w];
+            while (word) {
+                const int key = w * 32 + __ffs((int)word) - 1;
+                word &= word - 1;
+                const int k = (key >= HW) + (key >= 2 * HW) + (key >= 3 * HW);
+                Corners c;
+                splat_corners(fl, key - k * HW, H, W, c);
+                keys[pos] = key;
+                wts[pos] = k == 0 ? c.w[0] : k == 1 ? c.w[1] : k == 2 ? c.w[2] : c.w[3];
+                ++pos;
+            }
+        }
+        __syncthreads();
+    }
+}
+static void ss_launch_sort_wg(int* ws, const float* flow, int nflows, int H, int W, long long per, hipStream_t st) {
+    const int HW = H * W, words = ss_bitmap_words(HW);
+    hipLaunchKernelGGL(ss_sort_wg_kernel, dim3(cdiv(HW, 256), nflows), dim3(256), (size_t)words * 4, st, flow, ws, H, W, per, words);
+}
+
+__device__ __forceinline__ int ss_key_source(int key, int HW) {      // key = corner * HW + source, corner 0..3
+    if (key >= 2 * HW) key -= 2 * HW;
+    return key >= HW ? key - HW : key;
+}
+__device__ __forceinline__ float ss_normaliser(float s, int eps_mode) {   // as splat_normalize_kernel forms it
+    if (eps_mode == 0) return s + 0.0000001f;
+    if (eps_mode == 1) return s == 0.0f ? 1.0f : s;
+    if (eps_mode == 2) return fmaxf(s, 0.0000001f);
+    return s;
+}
+// acc + ((v * f) * w), each product and the sum rounded on its own: the oracle's operations (a fused multiply-add is not)
+__device__ __forceinline__ float ss_term(float acc, float v, float f, float w) {
+#pragma clang fp contract(off)
+    const float p = (v * f) * w;
+    return acc + p;
+}
+
+// 64 consecutive targets per workgroup, one per lane; the output channels [c0, c1) of this workgroup's slice strided over its
+// waves.  Every wave forms its targets' normaliser itself (one more channel), so neither waves nor slices depend on each other.
+// Targets with more than SSF_LONG entries are left out of the lane phase and then taken one after the other by the whole
+// workgroup: one channel per thread, the segment walked in the same order.
+__global__ __launch_bounds__(64 * SSF_WAVES) void ss_gather_f32_kernel(const mofa_softsplat_gather_args a, int chunk, long long per) {
+    __shared__ float long_norm;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int slice = blockIdx.y, n = blockIdx.z;
+    const int HW = a.H * a.W, C = a.C, prep = a.prep;
+    const bool normed = a.normalize != 0;
+    const int Co = C - ((normed && prep == 0) ? 1 : 0);      // channels of out; 'avg-<suffix>': the input's last one normalises
+    const int c0 = slice * chunk, c1 = min(c0 + chunk, Co);
+    const int* base = (const int*)a.ws + per * n;
+    const int* offset = base + HW;
+    const int* keys = base + 3 * HW + 1;
+    const float* wts = (const float*)(base + 3 * HW + 1 + 4 * HW);
+    const float* in = a.in + (size_t)n * C * HW;
+    const float* metric = a.metric ? a.metric + (size_t)n * HW : nullptr;
+    const float* nplane = prep == 0 ? in + (size_t)(C - 1) * HW : nullptr;   // the normaliser's own plane, if it has one
+    float* out = a.out + (size_t)n * Co * HW;
+    float* norm = (a.norm && slice == 0) ? a.norm + (size_t)n * HW : nullptr;
+    const int t = blockIdx.x * 64 + lane;
+    int ja = 0, jb = 0;
+    if (t < HW) {
+        ja = offset[t];
+        jb = offset[t + 1];
+    }
+    const bool is_long = jb - ja > SSF_LONG;
+    if (t < HW && !is_long) {
+        int rs[SSF_REG];
+        float rw[SSF_REG], rf[SSF_REG];
+#pragma unroll
+        for (int k = 0; k < SSF_REG; ++k) {
+            const bool on = ja + k < jb;
+            rs[k] = on ? ss_key_source(keys[ja + k], HW) : 0;
+            rw[k] = on ? wts[ja + k] : 0.0f;
+            rf[k] = on ? ss_prep_factor(metric, prep, rs[k]) : 0.0f;
+        }
+        float d = 1.0f;
+        if (normed) {
+            float s = 0.0f;
+#pragma unroll
+            for (int k = 0; k < SSF_REG; ++k)
+                if (ja + k < jb) s = ss_term(s, nplane ? nplane[rs[k]] : 1.0f, rf[k], rw[k]);
+            for (int j = ja + SSF_REG; j < jb; ++j) {
+                const int src = ss_key_source(keys[j], HW);
+                s = ss_term(s, nplane ? nplane[src] : 1.0f, ss_prep_factor(metric, prep, src), wts[j]);
+            }
+            if (norm && wave == 0) norm[t] = s;
+            d = ss_normaliser(s, a.eps_mode);
+        }
+        for (int c = c0 + wave; c < c1; c += SSF_WAVES) {
+            const float* plane = in + (size_t)c * HW;
+            float v[SSF_REG];
+#pragma unroll
+            for (int k = 0; k < SSF_REG; ++k) v[k] = ja + k < jb ? plane[rs[k]] : 0.0f;
+            float acc = 0.0f;
+#pragma unroll
+            for (int k = 0; k < SSF_REG; ++k)
+                if (ja + k < jb) acc = ss_term(acc, v[k], rf[k], rw[k]);
+            for (int j = ja + SSF_REG; j < jb; ++j) {
+                const int src = ss_key_source(keys[j], HW);
+                acc = ss_term(acc, plane[src], ss_prep_factor(metric, prep, src), wts[j]);
+            }
+            out[(size_t)c * HW + t] = normed ? acc / d : acc;
+        }
+    }
+    // the long targets of this workgroup, in target order (the ballot is the same in every wave: they hold the same 64 targets)
+    unsigned long long todo = __ballot(t < HW && is_long);
+    const int items = (c1 - c0) + (normed ? 1 : 0);            // item c1 - c0 is the normaliser
+    while (todo) {
+        const int l = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int tl = blockIdx.x * 64 + l;
+        const int la = offset[tl], lb = offset[tl + 1];
+        for (int i = threadIdx.x; i < items; i += 64 * SSF_WAVES) {
+            const bool is_norm = i == c1 - c0;
+            const float* plane = is_norm ? nplane : in + (size_t)(c0 + i) * HW;
+            float acc = 0.0f;
+#pragma unroll 4
+            for (int j = la; j < lb; ++j) {
+                const int src = ss_key_source(keys[j], HW);
+                acc = ss_term(acc, plane ? plane[src] : 1.0f, ss_prep_factor(metric, prep, src), wts[j]);
+            }
+            if (is_norm) long_norm = acc;
+            else out[(size_t)(c0 + i) * HW + tl] = acc;
+        }
+        if (normed) {                                          // (uniform: every thread of the workgroup walks the same `todo`)
+            __syncthreads();
+            const float s = long_norm;
+            const float d = ss_normaliser(s, a.eps_mode);
+            for (int i = threadIdx.x; i < c1 - c0; i += 64 * SSF_WAVES) {
+                float* o = out + (size_t)(c0 + i) * HW + tl;   // this thread's own raw sum
+                *o = *o / d;
+            }
+            if (norm && threadIdx.x == 0) norm[tl] = s;
+            __syncthreads();
+        }
+    }
+}
+
+extern "C" int mofa_softsplat_gather_f32(const mofa_softsplat_gather_args* a, mofa_stream_t stream) {
+    if (!a || !a->in || !a->flow || !a->out || !a->ws || a->N <= 0 || a->N > 65535 || a->C <= 0 || !ss_plane_ok(a->H, a->W))
+        return MOFA_EINVAL;
+    if (a->prep < 0 || a->prep > 3 || a->eps_mode < 0 || a->eps_mode > 3 || (a->normalize != 0 && a->normalize != 1)) return MOFA_EINVAL;
+    if (a->reserved[0] || a->reserved[1] || a->reserved[2] || a->reserved[3]) return MOFA_EINVAL;
+    if ((a->prep >= 2) != (a->metric != nullptr) || (a->prep >= 1 && !a->normalize) || (a->norm && !a->normalize)) return MOFA_EINVAL;
+    const int Co = a->C - ((a->normalize && a->prep == 0) ? 1 : 0);
+    if (Co <= 0 || a->slices < 1 || a->slices > Co || a->slices > 65535) return MOFA_EINVAL;
+    const int HW = a->H * a->W;
+    const int chunk = (Co + a->slices - 1) / a->slices;
+    hipStream_t st = (hipStream_t)stream;
+    if (ss_build_csr(a->flow, a->ws, a->N, a->H, a->W, st, ss_wg_sort_fits(HW)) != MOFA_OK) return MOFA_ELAUNCH;
+    hipLaunchKernelGGL(ss_gather_f32_kernel, dim3(cdiv(HW, 64), a->slices, a->N), dim3(64 * SSF_WAVES), 0, st, *a, chunk,
+                       (long long)ws_ints_per_flow(HW));
     MOFA_CHECK_LAUNCH();
     return MOFA_OK;
 }

@@ -70,6 +70,15 @@ class SoftsplatGradArgs(C.Structure):
     ]
 
 
+class SoftsplatGatherArgs(C.Structure):
+    _fields_ = [
+        ("inp", C.c_void_p), ("flow", C.c_void_p), ("metric", C.c_void_p), ("out", C.c_void_p), ("norm", C.c_void_p), ("ws", C.c_void_p),
+        ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("prep", C.c_int32), ("normalize", C.c_int32),
+        ("eps_mode", C.c_int32), ("slices", C.c_int32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
 # name -> argtypes (every symbol include/mofa_hip.h declares; tests check they all resolve)
@@ -118,6 +127,7 @@ PROTOTYPES = {
     "mofa_softsplat_norm_f32": [_P, _P, _P, _I, _I, _I, _P],
     "mofa_softsplat_grad_prologue_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mofa_softsplat_grad_f32": [_P, _P],            # (const mofa_softsplat_grad_args*: a byref(SoftsplatGradArgs), 120 bytes)
+    "mofa_softsplat_gather_f32": [_P, _P],          # (const mofa_softsplat_gather_args*: a byref(SoftsplatGatherArgs), 96 bytes)
     "mofa_flow_downscale_f32": [_P, _P, _I, _I, _I, _I, _P],
     "mofa_prepare_model_input": [_P, _P, _P, _I, _I, _I, _F, _P],
     "mofa_cfg_euler_step": [_P, _P, _I, _I, _I, _F, _F, _F, _F, _P],

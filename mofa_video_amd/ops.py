@@ -740,6 +740,39 @@ def softsplat_grad_f32(grad, flow, Cc, prep=0, tenIn=None, metric=None, inv=None
     return dI, dF, dm
 
 
+def softsplat_gather_slices(N, Co, HW):
+    """channel slices of mofa_softsplat_gather_f32 for a shape, by the rule of softsplat_grad_slices (the result does not depend on
+    them: every slice forms the normaliser itself)"""
+    return softsplat_grad_slices(N, Co, HW)
+
+
+def softsplat_gather_f32(tenIn, tenFlow, tenMetric=None, prep=0, normalize=False, eps_mode=0, want_norm=False, slices=None):
+    """the forward of every mode as one deterministic fp32 gather (include/mofa_hip.h, mofa_softsplat_gather_f32): tenIn fp32
+    [N,C,H,W], tenFlow fp32 [N,2,H,W], tenMetric fp32 [N,1,H,W] (prep 2 / 3) -> (out fp32 [N,Co,H,W], the splatted normaliser
+    fp32 [N,1,H,W] before its eps handling or None)"""
+    lib = L.load()
+    _chk(tenIn, F32); _chk(tenFlow, F32)
+    N, Cc, H, W = tenIn.shape
+    assert tuple(tenFlow.shape) == (N, 2, H, W)
+    if tenMetric is not None:
+        _chk(tenMetric, F32)
+        assert tenMetric.numel() == N * H * W
+    Co = Cc - (1 if normalize and prep == 0 else 0)
+    keep = [tenIn.contiguous(), tenFlow.contiguous(), tenMetric.contiguous() if tenMetric is not None else None]
+    out = torch.empty((N, Co, H, W), dtype=F32, device=tenIn.device)
+    norm = torch.empty((N, 1, H, W), dtype=F32, device=tenIn.device) if want_norm else None
+    ws = torch.empty((lib.mofa_softsplat_ws_bytes(N, H, W),), dtype=torch.uint8, device=tenIn.device)
+    if slices is None:
+        slices = softsplat_gather_slices(N, Co, H * W)
+    a = L.SoftsplatGatherArgs(*[L.ptr(t) for t in keep], L.ptr(out), L.ptr(norm), L.ptr(ws), N, Cc, H, W, prep, int(bool(normalize)),
+                              eps_mode, slices)
+    t0 = TIMER.start() if TIMER is not None else None
+    L.check(lib.mofa_softsplat_gather_f32(C.byref(a), L.stream_ptr()), "mofa_softsplat_gather_f32")
+    if t0 is not None:       # per image: I gathered + out written (8 C H W), the flow, at most 4 HW CSR entries of 8 bytes
+        TIMER.stop("softsplat_gather_f32", t0, nbytes=float(N) * H * W * (8.0 * Cc + 8.0 + 32.0))
+    return out, norm
+
+
 def flow_downscale(flow, s):
     lib = L.load()
     _chk(flow, F32)

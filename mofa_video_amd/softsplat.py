@@ -15,11 +15,26 @@ through ``softsplat_func`` (softsplat_func.backward, softsplat.py:349-524), the 
 normalisation as well.  Gradients are fp32 (cast back to an input's dtype by autograd) and reproducible bit for bit; the
 forward values are the same with and without grad tracking ('avg' stays the fp16 gather; its backward treats that rounding as
 identity).  Double backward is not supported.
+
+``GATHER_F32`` (initial value: ``MOFA_SOFTSPLAT_GATHER_F32=1`` in the environment; read at every call; off by default) runs every
+mode as one call of the deterministic fp32 gather (include/mofa_hip.h, mofa_softsplat_gather_f32) instead: fp32 end to end as the
+reference computes it, the same bits in every run and with or without grad tracking, and the normaliser it returns saves the
+'avg' backward its second CSR build.  With the switch off, ``torch.use_deterministic_algorithms(True)`` moves the modes that would
+use the atomicAdd scatter onto that path; 'avg' keeps its fp16 gather, which is deterministic already.
 """
+import os
+
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import ops
+
+GATHER_F32 = os.environ.get("MOFA_SOFTSPLAT_GATHER_F32") == "1"
+
+
+def _use_gather_f32(strMode, gather_f32, deterministic):
+    """whether a mode's forward is the fp32 gather: always with the switch; under torch's deterministic flag, every mode but 'avg'"""
+    return bool(gather_f32) or (bool(deterministic) and strMode != 'avg')
 
 
 def _prep(strMode):
@@ -32,9 +47,15 @@ def _eps_mode(strMode):
     return 0 if len(parts) == 1 or parts[1] == 'addeps' else {'zeroeps': 1, 'clipeps': 2}.get(parts[1], 3)
 
 
-def _splat(tenIn, tenFlow, tenMetric, strMode):
-    """the forward of every mode -> (output, the splatted normaliser channel [N,1,H,W] or None: 'sum*' and 'avg')"""
+def _splat(tenIn, tenFlow, tenMetric, strMode, want_norm=False):
+    """the forward of every mode -> (output, the splatted normaliser channel [N,1,H,W] or None: 'sum*', and 'avg' on the fp16 path);
+    want_norm: the fp32 gather returns the normaliser as well (its output does not depend on that)"""
     N, C, H, W = tenIn.shape
+    if _use_gather_f32(strMode, GATHER_F32, torch.are_deterministic_algorithms_enabled()):
+        prep, normalize = _prep(strMode), strMode.split('-')[0] != 'sum'
+        return ops.softsplat_gather_f32(tenIn.float().contiguous(), tenFlow.float().contiguous(),
+                                        tenMetric.float().contiguous() if prep >= 2 else None, prep, normalize,
+                                        _eps_mode(strMode) if normalize else 0, want_norm=want_norm and normalize)
     if strMode.split('-')[0] == 'sum':       # 'sum' and 'sum-<suffix>': the raw splat, nothing is normalised (softsplat.py:252)
         return ops.softsplat_scatter_f32(tenIn.float().contiguous(), tenFlow.float().contiguous()), None
     if strMode == 'avg':
@@ -66,7 +87,7 @@ class softsplat_func(torch.autograd.Function):
         assert tenIn.is_cuda and tenFlow.is_cuda, "softsplat: CUDA/HIP tensors required (as in the reference)"
         tenIn, tenFlow = tenIn.float().contiguous(), tenFlow.float().contiguous()
         assert tenFlow.shape == (tenIn.shape[0], 2, tenIn.shape[2], tenIn.shape[3])
-        out = ops.softsplat_scatter_f32(tenIn, tenFlow)
+        out = _splat(tenIn, tenFlow, None, 'sum')[0]
         ctx.save_for_backward(tenIn if ctx.needs_input_grad[1] else None, tenFlow)
         return out
 
@@ -87,7 +108,7 @@ class _softsplat_normalized(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, tenIn, tenFlow, tenMetric, strMode):
-        out, norm = _splat(tenIn, tenFlow, tenMetric, strMode)
+        out, norm = _splat(tenIn, tenFlow, tenMetric, strMode, want_norm=True)
         need_in = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         ctx.strMode, ctx.C = strMode, tenIn.shape[1]
         ctx.save_for_backward(tenIn.float().contiguous() if need_in else None, tenFlow.float().contiguous(),
@@ -101,7 +122,7 @@ class _softsplat_normalized(torch.autograd.Function):
     def backward(ctx, tenOutgrad):
         tenIn, tenFlow, tenMetric, out, norm = ctx.saved_tensors
         g = tenOutgrad.float().contiguous()
-        if ctx.strMode == 'avg':
+        if norm is None:                      # 'avg' on the fp16 path (the fp32 gather returned its normaliser with the output)
             norm = ops.softsplat_norm_f32(tenFlow)
         inv, glast = ops.softsplat_grad_prologue_f32(g, out, norm, _eps_mode(ctx.strMode))
         dI, dF, dm = ops.softsplat_grad_f32(g, tenFlow, ctx.C, _prep(ctx.strMode), tenIn=tenIn, metric=tenMetric, inv=inv, glast=glast,
