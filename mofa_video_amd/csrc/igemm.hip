@@ -504,7 +504,7 @@ extern "C" int mofa_igemm_f16(const mofa_igemm_args* a, mofa_stream_t stream) {
     if (n_cu == 0) return MOFA_ELAUNCH;
     n_cu = n_cu >= 8 ? (n_cu / 8) * 8 : 8;                    // persistent grids are multiples of 8 (one per XCD): every tile /
                                                               // round / split-K count below uses the SAME rounded figure
-    const int taps = a->mode == MOFA_MODE_CONV3X3 ? (a->ksize > 0 ? a->ksize * a->ksize : 9) : (a->mode == MOFA_MODE_CONVT3 ? 3 : 1);
+    const int taps = igemm_taps(*a);
     const long long Ktot = (long long)taps * a->Cin;
     const int kind = a->act == MOFA_ACT_GEGLU_PAIR ? 8 : ((a->r1 ? 1 : 0) | (a->r2 ? 2 : 0) | (a->rowvec ? 4 : 0));
     int choice = a->tile;                                     // MOFA_TILE_* or 0 = cost model
@@ -578,8 +578,7 @@ extern "C" int mofa_igemm_f16(const mofa_igemm_args* a, mofa_stream_t stream) {
     const long long nt = (long long)tilesM * tilesN;
     if (nt > 0x7fffffffLL) return MOFA_EINVAL;
     const int slots = n_cu * c.wg_per_cu;                     // resident workgroups (a multiple of 8 on gfx950)
-    int grid = (int)(nt < slots ? ((nt + 7) / 8) * 8 : (slots / 8) * 8);
-    if (grid < 8) grid = 8;
+    const int grid = igemm_grid(nt, slots);
     hipLaunchKernelGGL(c.k[kind], dim3(grid), dim3(c.threads), c.lds, (hipStream_t)stream, *a, tilesN, (int)nt);
     MOFA_CHECK_LAUNCH();
     return MOFA_OK;

@@ -48,6 +48,9 @@ constexpr int BIAS0 = 2 * SLOT;                                // per wave 2 x 7
 constexpr int LDS_BYTES3 = BIAS0 + 8 * 2 * 768;                // 159744 (the epilogue transposes through a free ring plane)
 constexpr int LOOKAHEAD3 = 4 + NJ3;                            // DMA instructions of the last two phases may be in flight
 
+// epilogue scratch row r (128 bytes) of a wave: rows 8 b .. 8 b + 7 in its 1 KB block b, the blocks 8 KB apart (see the kernel)
+struct ScratchRows { __device__ __forceinline__ int operator()(int r) const { return (r >> 3) * 8192 + (r & 7) * 128; } };
+
 struct Cursor3 {                    // one K-half plane of the persistent K-tile stream
     int local;                      // walk position of the output tile it is in
     int ikc, ksw, ky, kx;           // K tile within the tap / overall, tap coordinates (convT3: ky = tap)
@@ -89,51 +92,13 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     // plane p of a K tile = 16 X pieces + 20 W pieces of 16 rows x 64 B; wave w issues X pieces w, w + 8, W pieces w, w + 8
     // and, when p == grp, W piece 16 + (w & 3).  Lane l of a piece: row l / 4, slot l % 4 <- source chunk slot ^ ((row >> 2) & 3)
     // = slot ^ ((l >> 4) & 3) (piece rows start at multiples of 16)
-    auto lane_now = [&]() __attribute__((always_inline)) { int l = lane; asm volatile("" : "+v"(l)); return l; };
     auto swz_bytes = [&](int l, int p) __attribute__((always_inline)) { return (((l & 3) ^ ((l >> 4) & 3)) * 16 + p * RBH); };
-    const int ks_ = a.ksize > 0 ? a.ksize : 3, dil_ = a.dil > 0 ? a.dil : 1;
-    const int org_ = a.pad == MOFA_PAD_TRAILING ? 0 : (ks_ >> 1);
-    auto pack_geo = [&](int m) __attribute__((always_inline)) -> int {
-        int g = m;
-        if (a.mode == MOFA_MODE_CONV3X3) {
-            const int img = fdiv(m, aux.hw), rem = m - img * (a.Hout * a.Wout);
-            const int oy = fdiv(rem, aux.wout);
-            g = (img << 20) | (oy << 10) | (rem - oy * a.Wout);
-        } else if (a.mode == MOFA_MODE_CONVT3) {
-            int lo = 1, hi = 1;
-            if (a.T > 0) {
-                const int fr = fdiv(m, aux.t3hw);
-                const int f = fr - fdiv(fr, aux.t3t) * a.T;
-                lo = f > 0; hi = f < a.T - 1;
-            }
-            g = m | (lo << 29) | (hi << 30);
-        }
-        return m < a.M ? g : -1;
-    };
+    const TapGeo tg(a);
     // W pieces w + 8 and 16 + (w & 3) start 128 and 256 + 16 (w & 3) - 16 w rows after piece w (uniform byte distances)
     const unsigned wd1 = 128u * (unsigned)(Ktot * 2), wd2 = (unsigned)(256 + 16 * (wave & 3) - 16 * wave) * (unsigned)(Ktot * 2);
     constexpr unsigned W_DEAD = 0x80000000u;                       // past the end of the walk: beyond any weight tensor (< 2 GB)
-    const auto rsx = __builtin_amdgcn_make_buffer_rsrc((void*)aux.xbase, 0, aux.x_bytes, 0x00020000);
-    const auto rsw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, aux.w_bytes, 0x00020000);
-    auto bglds16 = [&](const decltype(rsx)& rs, unsigned voff, int soff, char* lds_wave_base) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-    };
-    auto tap_src = [&](int g, int ky, int kx, int swzb) __attribute__((always_inline)) -> unsigned {   // bytes from aux.xbase
-        int row = g;
-        bool ok = g >= 0;
-        if (a.mode == MOFA_MODE_CONV3X3) {
-            const int vy = ((g >> 10) & 1023) * a.stride + (ky - org_) * dil_;
-            const int vx = (g & 1023) * a.stride + (kx - org_) * dil_;
-            ok = ok && vy >= 0 && vx >= 0 && vy < a.Hin * a.up && vx < a.Win * a.up;
-            const int iy = (a.up == 2) ? (vy >> 1) : vy, ix = (a.up == 2) ? (vx >> 1) : vx;
-            row = ((g >> 20) * a.Hin + iy) * a.Win + ix;
-        } else if (a.mode == MOFA_MODE_CONVT3) {
-            ok = ok && !(ky == 0 && !((g >> 29) & 1)) && !(ky == 2 && !((g >> 30) & 1));
-            row = (g & 0x1fffffff) + (ky - 1) * a.HW + aux.row_shift;
-        }
-        const unsigned off = (unsigned)row * (unsigned)aux.ldxb + (unsigned)swzb;
-        return ok ? off : XO_INVALID;
-    };
+    const BufRsrc rsx = buf_rsrc(aux.xbase, aux.x_bytes), rsw = buf_rsrc(a.w, aux.w_bytes);
+    const LdsDma16 bglds16;
     // position in the workgroup's stream -> output tile and K-tile range [kb, ke)
     auto item_decode = [&](int phase, int local, int& tile, int& kb, int& ke) __attribute__((always_inline)) {
         tile = walk.start + (phase == 0 ? local : 0); kb = 0; ke = nk;
@@ -160,8 +125,8 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
         int tile, kb, ke;
         item_decode(c.phase, c.local, tile, kb, ke);
         const int tm = fdiv(tile, aux.tiles_n), tn = tile - tm * tilesN;
-        const int l = lane_now(), r_l = l >> 2;
-        const int g0 = pack_geo(tm * TBM3 + 16 * wave + r_l), g1 = pack_geo(tm * TBM3 + 16 * (wave + 8) + r_l);
+        const int l = lane_now(lane), r_l = l >> 2;
+        const int g0 = pack_geo(a, aux, tm * TBM3 + 16 * wave + r_l), g1 = pack_geo(a, aux, tm * TBM3 + 16 * (wave + 8) + r_l);
         c.gx0 = live ? g0 : -1;
         c.gx1 = live ? g1 : -1;
         const unsigned wo = (unsigned)(tn * TBN3 + 16 * wave + r_l) * (unsigned)(Ktot * 2) + swz_bytes(l, p);
@@ -172,16 +137,16 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
             int tap = fdiv(kb, aux.kpt_d);
             c.ikc = kb - tap * kpt;
             c.ksw = kb;
-            if (a.mode == MOFA_MODE_CONV3X3) { c.ky = fdiv(tap, aux.ks_d); c.kx = tap - c.ky * ks_; } else c.ky = tap;
-            c.xo0 = tap_src(c.gx0, c.ky, c.kx, swz_bytes(l, p));
-            c.xo1 = tap_src(c.gx1, c.ky, c.kx, swz_bytes(l, p));
+            if (a.mode == MOFA_MODE_CONV3X3) { c.ky = fdiv(tap, aux.ks_d); c.kx = tap - c.ky * tg.ks; } else c.ky = tap;
+            c.xo0 = tap_src(a, aux, tg, c.gx0, c.ky, c.kx, swz_bytes(l, p));
+            c.xo1 = tap_src(a, aux, tg, c.gx1, c.ky, c.kx, swz_bytes(l, p));
         }
     };
     auto issue = [&](Cursor3& c, const int p, const int slot) __attribute__((always_inline)) {
         if (c.ikc == 0) {
-            const int l = lane_now();
-            c.xo0 = tap_src(c.gx0, c.ky, c.kx, swz_bytes(l, p));
-            c.xo1 = tap_src(c.gx1, c.ky, c.kx, swz_bytes(l, p));
+            const int l = lane_now(lane);
+            c.xo0 = tap_src(a, aux, tg, c.gx0, c.ky, c.kx, swz_bytes(l, p));
+            c.xo1 = tap_src(a, aux, tg, c.gx1, c.ky, c.kx, swz_bytes(l, p));
         }
         char* pl = smem + slot + p * PLANE;
         const int wk = c.ksw * 128;
@@ -192,11 +157,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
         if (grp == p) bglds16(rsw, c.wo0 + wd2, wk, pl + XPL + (16 + (wave & 3)) * 1024);
     };
     auto advance = [&](Cursor3& c, const int p) __attribute__((always_inline)) {
-        ++c.ksw;
-        if (++c.ikc == kpt) {
-            c.ikc = 0;
-            if (a.mode == MOFA_MODE_CONV3X3) { if (++c.kx == ks_) { c.kx = 0; ++c.ky; } } else ++c.ky;
-        }
+        tap_advance(c, a, kpt, tg.ks);
         if (c.ksw == c.kend) { next_pos(c.phase, c.local); cur_setup(c, p); }
     };
 
@@ -218,14 +179,14 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     // first version loaded the bias straight from global memory at tile start; tools/bias_probe.py shows no measurable
     // difference between the two, nor between bias and no bias -- its first reading, "bias costs 15 %", was the slower first
     // measurement after fresh allocations.)
-    const auto rsb = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? (unsigned)a.N * 4u : 0u, 0x00020000);
+    const BufRsrc rsb = buf_rsrc(a.bias, a.bias ? (unsigned)a.N * 4u : 0u);
     char* bias_lds = smem + BIAS0 + wave * 1536;
     auto bias_prefetch = [&](int phase_, int local_, int slot) __attribute__((always_inline)) {
         if (phase_ != 0) return;                                   // (a split-K item starts from zero; past the end: nothing)
         int tile_, kb_, ke_;
         item_decode(phase_, local_, tile_, kb_, ke_);
         const int tm_ = fdiv(tile_, aux.tiles_n), tn_ = tile_ - tm_ * tilesN;
-        const unsigned n0 = (unsigned)(tn_ * TBN3 + wn * NJ3 * 32 + lane_now());
+        const unsigned n0 = (unsigned)(tn_ * TBN3 + wn * NJ3 * 32 + lane_now(lane));
 #pragma unroll
         for (int k = 0; k < 3; ++k)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (__attribute__((address_space(3))) void*)(bias_lds + slot * 768 + k * 256), 4,
@@ -287,14 +248,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     // blocks it will DMA into itself (X pieces w, w + 8 and W pieces w, w + 8 of that plane: 8 KB apart): 32 rows x 128 B,
     // rows 8 b .. 8 b + 7 in block b.  No other wave touches those blocks before its fragment reads two barriers later, the
     // wave's own DMA is issued after its epilogue (program order, lgkmcnt(0) at the end), and no barrier is needed.
-    auto srow = [&](int r) __attribute__((always_inline)) { return (r >> 3) * 8192 + (r & 7) * 128; };
-    auto act_apply = [&](auto ac, float v) __attribute__((always_inline)) -> float {
-        constexpr int ACT = decltype(ac)::v;
-        if constexpr (ACT == MOFA_ACT_SILU) return silu_f(v);
-        else if constexpr (ACT == MOFA_ACT_RELU) return fmaxf(v, 0.0f);
-        else if constexpr (ACT == MOFA_ACT_GELU) return gelu_erf_f(v);
-        else return v;
-    };
+    const ScratchRows srow;
     // register r of accumulator tile (i, j) is row 32 i + l31, column 32 j + 8 (r >> 2) + 4 lh + (r & 3)
     // ---- no residual, no per-row vector: activation in the fragment layout, fp16; two accumulator tiles (64 columns) per
     //      transpose so that a store instruction covers 8 whole 128-byte rows.  The wave's 160 columns start at byte 0 (wn = 0)
@@ -303,13 +257,12 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     auto epilogue_light = [&](auto ac, auto wnc, f32x16 (&acc)[MI3][NJ3], const int mw, const int nw, char* eb) __attribute__((always_inline)) {
         constexpr int J0 = decltype(wnc)::v ? 1 : 0;   // first tile of the first pair
         constexpr int JS = decltype(wnc)::v ? 0 : 4;                 // the tile without a partner
-        const int lane_e = lane_now();                             // (lane-derived offsets are not kept live across the K loop)
+        const int lane_e = lane_now(lane);                         // (lane-derived offsets are not kept live across the K loop)
         const int lane = lane_e, l31 = lane & 31, lh = lane >> 5;
         f16* out = (f16*)a.out;
         float saccv = a.s_acc;                                     // VGPR operand on purpose (see igemm.hip's epilogue)
         asm volatile("" : "+v"(saccv));
         char* wr = eb + srow(l31);
-        const int wsw = (l31 >> 1) & 7, wpar = l31 & 1;
 #pragma unroll
         for (int i = 0; i < MI3; ++i) {
 #pragma unroll
@@ -323,16 +276,13 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = (f16)act_apply(ac, saccv * acc[i][j0 + jj][4 * g + e]);
                         const int c8 = 8 * jj + 2 * g + lh;
-                        *(f16x4*)(wr + (((c8 >> 1) ^ wsw) << 4) + (((c8 & 1) ^ wpar) << 3)) = o;
+                        *(f16x4*)h16_off(wr, l31, c8) = o;
                     }
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
-                    const int row = 8 * p + (lane >> 3), blk = lane & 7;
-                    const f16x8 v = *(const f16x8*)(eb + srow(row) + ((blk ^ ((row >> 1) & 7)) << 4));
-                    f16x8 o = v;
-                    if (row & 1) o = (f16x8){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
-                    const int mr = mw + 32 * i + row, n = nw + 32 * j0 + 8 * blk;
-                    if (mr < a.M && n + 8 <= a.N) *(f16x8*)(out + (size_t)mr * a.ldo + n) = o;
+                    const H16Piece r = h16_row<8>(eb, srow, lane, p);
+                    const int mr = mw + 32 * i + r.row, n = nw + 32 * j0 + 8 * r.blk;
+                    if (mr < a.M && n + 8 <= a.N) *(f16x8*)(out + (size_t)mr * a.ldo + n) = r.v;
                 }
             }
             {                                                      // the single tile: 32 columns per row
@@ -342,16 +292,13 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = (f16)act_apply(ac, saccv * acc[i][JS][4 * g + e]);
                     const int c8 = 2 * g + lh;
-                    *(f16x4*)(wr + (((c8 >> 1) ^ wsw) << 4) + (((c8 & 1) ^ wpar) << 3)) = o;
+                    *(f16x4*)h16_off(wr, l31, c8) = o;
                 }
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
-                    const int row = 16 * p + (lane >> 2), blk = lane & 3;
-                    const f16x8 v = *(const f16x8*)(eb + srow(row) + ((blk ^ ((row >> 1) & 7)) << 4));
-                    f16x8 o = v;
-                    if (row & 1) o = (f16x8){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
-                    const int mr = mw + 32 * i + row, n = nw + 32 * JS + 8 * blk;
-                    if (mr < a.M && n + 8 <= a.N) *(f16x8*)(out + (size_t)mr * a.ldo + n) = o;
+                    const H16Piece r = h16_row<4>(eb, srow, lane, p);
+                    const int mr = mw + 32 * i + r.row, n = nw + 32 * JS + 8 * r.blk;
+                    if (mr < a.M && n + 8 <= a.N) *(f16x8*)(out + (size_t)mr * a.ldo + n) = r.v;
                 }
             }
         }
@@ -368,7 +315,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
         constexpr int JS = decltype(wnc)::v ? 0 : 4;                 // the tile without a partner
         constexpr bool UNIT = decltype(unit)::v != 0;                // one residual, s1 == 1: packed fp16 adds
         constexpr int PPI = 10, NP = MI3 * PPI;       // store pieces (16 bytes per lane) per row tile / per tile
-        const int lane_e = lane_now();
+        const int lane_e = lane_now(lane);
         const int lane = lane_e, l31 = lane & 31, lh = lane >> 5;
         f16* out = (f16*)a.out;
         const f16* r1 = (const f16*)a.r1;
@@ -417,7 +364,6 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
             if (st + D < NP) piece_loads(st + D, st % D);           // refill the ring slot just consumed
         };
         char* wr = eb + srow(l31);
-        const int wsw = (l31 >> 1) & 7, wpar = l31 & 1;
 #pragma unroll
         for (int i = 0; i < MI3; ++i) {
 #pragma unroll
@@ -431,15 +377,12 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = (f16)(saccv * acc[i][j0 + jj][4 * g + e]);
                         const int c8 = 8 * jj + 2 * g + lh;
-                        *(f16x4*)(wr + (((c8 >> 1) ^ wsw) << 4) + (((c8 & 1) ^ wpar) << 3)) = o;
+                        *(f16x4*)h16_off(wr, l31, c8) = o;
                     }
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
-                    const int row = 8 * p + (lane >> 3), blk = lane & 7;
-                    const f16x8 v = *(const f16x8*)(eb + srow(row) + ((blk ^ ((row >> 1) & 7)) << 4));
-                    f16x8 o = v;
-                    if (row & 1) o = (f16x8){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
-                    finish(i * PPI + pr * 4 + p, o);
+                    const H16Piece r = h16_row<8>(eb, srow, lane, p);
+                    finish(i * PPI + pr * 4 + p, r.v);
                 }
             }
             {                                                      // the single tile: 32 columns per row
@@ -449,15 +392,12 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = (f16)(saccv * acc[i][JS][4 * g + e]);
                     const int c8 = 2 * g + lh;
-                    *(f16x4*)(wr + (((c8 >> 1) ^ wsw) << 4) + (((c8 & 1) ^ wpar) << 3)) = o;
+                    *(f16x4*)h16_off(wr, l31, c8) = o;
                 }
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
-                    const int row = 16 * p + (lane >> 2), blk = lane & 3;
-                    const f16x8 v = *(const f16x8*)(eb + srow(row) + ((blk ^ ((row >> 1) & 7)) << 4));
-                    f16x8 o = v;
-                    if (row & 1) o = (f16x8){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
-                    finish(i * PPI + 8 + p, o);
+                    const H16Piece r = h16_row<4>(eb, srow, lane, p);
+                    finish(i * PPI + 8 + p, r.v);
                 }
             }
         }
@@ -472,7 +412,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     auto epilogue_stats = [&](auto wnc, f32x16 (&acc)[MI3][NJ3], const int mw, const int nw, char* eb) __attribute__((always_inline)) {
         constexpr int J0 = decltype(wnc)::v ? 1 : 0, JS = decltype(wnc)::v ? 0 : 4;
         constexpr int NP = 20;                                       // pieces: 2 sets x 2 row tiles x 4, then 2 row tiles x 2
-        const int lane_e = lane_now();
+        const int lane_e = lane_now(lane);
         const int lane = lane_e, l31 = lane & 31, lh = lane >> 5;
         f16* out = (f16*)a.out;
         const f16* r1 = (const f16*)a.r1;
@@ -538,7 +478,6 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
             }
         };
         char* wr = eb + srow(l31);
-        const int wsw = (l31 >> 1) & 7, wpar = l31 & 1;
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) {                           // the two pairs
             const int j0 = J0 + 2 * pr;
@@ -554,15 +493,12 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = (f16)(saccv * acc[i][j0 + jj][4 * g + e]);
                         const int c8 = 8 * jj + 2 * g + lh;
-                        *(f16x4*)(wr + (((c8 >> 1) ^ wsw) << 4) + (((c8 & 1) ^ wpar) << 3)) = o;
+                        *(f16x4*)h16_off(wr, l31, c8) = o;
                     }
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
-                    const int row = 8 * p + (lane >> 3), blk = lane & 7;
-                    const f16x8 v = *(const f16x8*)(eb + srow(row) + ((blk ^ ((row >> 1) & 7)) << 4));
-                    f16x8 o = v;
-                    if (row & 1) o = (f16x8){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
-                    finish(pr * 8 + i * 4 + p, o);
+                    const H16Piece r = h16_row<8>(eb, srow, lane, p);
+                    finish(pr * 8 + i * 4 + p, r.v);
                 }
             }
             reduce_store(8, nw + 32 * j0 + 8 * (lane & 7), lane < 8);
@@ -577,15 +513,12 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = (f16)(saccv * acc[i][JS][4 * g + e]);
                 const int c8 = 2 * g + lh;
-                *(f16x4*)(wr + (((c8 >> 1) ^ wsw) << 4) + (((c8 & 1) ^ wpar) << 3)) = o;
+                *(f16x4*)h16_off(wr, l31, c8) = o;
             }
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                const int row = 16 * p + (lane >> 2), blk = lane & 3;
-                const f16x8 v = *(const f16x8*)(eb + srow(row) + ((blk ^ ((row >> 1) & 7)) << 4));
-                f16x8 o = v;
-                if (row & 1) o = (f16x8){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
-                finish(16 + i * 2 + p, o);
+                const H16Piece r = h16_row<4>(eb, srow, lane, p);
+                finish(16 + i * 2 + p, r.v);
             }
         }
         reduce_store(4, nw + 32 * JS + 8 * (lane & 3), lane < 4);
@@ -598,14 +531,13 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     //      go through one 32 x 64 fp16 transpose and whole 128-byte row pieces, tile 4 (16 columns) through a second one ------
     auto epilogue_geglu = [&](auto s1c, f32x16 (&acc)[MI3][NJ3], const int mw, const int nw, char* eb) __attribute__((always_inline)) {
         constexpr bool SACC1 = decltype(s1c)::v != 0;              // s_acc == 1: the multiplies drop out
-        const int lane_e = lane_now();
+        const int lane_e = lane_now(lane);
         const int lane = lane_e, l31 = lane & 31, lh = lane >> 5;
         f16* out = (f16*)a.out;
         float saccv = a.s_acc;
         asm volatile("" : "+v"(saccv));
         const int nout = a.N / 2, no0 = nw / 2;                    // first output column of this wave
         char* wr = eb + srow(l31);
-        const int wsw = (l31 >> 1) & 7, wpar = l31 & 1;
         auto product = [&](int i, int j, int g) __attribute__((always_inline)) -> f16x4 {
             f16x4 o;
 #pragma unroll
@@ -623,29 +555,23 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
                     const int c8 = 4 * j + 2 * g + lh;             // 8-byte chunk (4 columns) of the 64-column row
-                    *(f16x4*)(wr + (((c8 >> 1) ^ wsw) << 4) + (((c8 & 1) ^ wpar) << 3)) = product(i, j, g);
+                    *(f16x4*)h16_off(wr, l31, c8) = product(i, j, g);
                 }
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
-                const int row = 8 * p + (lane >> 3), blk = lane & 7;
-                const f16x8 v = *(const f16x8*)(eb + srow(row) + ((blk ^ ((row >> 1) & 7)) << 4));
-                f16x8 o = v;
-                if (row & 1) o = (f16x8){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
-                const int mr = mw + 32 * i + row, n = no0 + 8 * blk;
-                if (mr < a.M && n + 8 <= nout) *(f16x8*)(out + (size_t)mr * a.ldo + n) = o;
+                const H16Piece r = h16_row<8>(eb, srow, lane, p);
+                const int mr = mw + 32 * i + r.row, n = no0 + 8 * r.blk;
+                if (mr < a.M && n + 8 <= nout) *(f16x8*)(out + (size_t)mr * a.ldo + n) = r.v;
             }
             {                                                      // tile 4: 16 columns per row
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
                     const int c8 = 2 * g + lh;
-                    *(f16x4*)(wr + (((c8 >> 1) ^ wsw) << 4) + (((c8 & 1) ^ wpar) << 3)) = product(i, 4, g);
+                    *(f16x4*)h16_off(wr, l31, c8) = product(i, 4, g);
                 }
-                const int row = lane >> 1, blk = lane & 1;
-                const f16x8 v = *(const f16x8*)(eb + srow(row) + ((blk ^ ((row >> 1) & 7)) << 4));
-                f16x8 o = v;
-                if (row & 1) o = (f16x8){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
-                const int mr = mw + 32 * i + row, n = no0 + 64 + 8 * blk;
-                if (mr < a.M && n + 8 <= nout) *(f16x8*)(out + (size_t)mr * a.ldo + n) = o;
+                const H16Piece r = h16_row<2>(eb, srow, lane, 0);
+                const int mr = mw + 32 * i + r.row, n = no0 + 64 + 8 * r.blk;
+                if (mr < a.M && n + 8 <= nout) *(f16x8*)(out + (size_t)mr * a.ldo + n) = r.v;
             }
         }
         wait_lds();
@@ -655,7 +581,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     auto epilogue_rows = [&](auto un, f32x16 (&acc)[MI3][NJ3], const int mw, const int nw, char* eb) __attribute__((always_inline)) {
         constexpr bool RVROW = RV && decltype(un)::v == 0;         // the row vector was NOT folded into the accumulators
         constexpr int STEPS = MI3 * NJ3;                           // (i, j): one accumulator tile per step
-        const int lane_e = lane_now();
+        const int lane_e = lane_now(lane);
         const int lane = lane_e, l31 = lane & 31, lh = lane >> 5;
         f16* out = (f16*)a.out;
         const f16* r1 = (const f16*)a.r1;
@@ -734,7 +660,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
 
     // ---- split-K: the fp32 partial tile, row-major [256][TBN], through the same 32 x 32 fp32 transposes ------------------------
     auto epilogue_dump = [&](f32x16 (&acc)[MI3][NJ3], float* wst, char* eb) __attribute__((always_inline)) {
-        const int lane_e = lane_now();
+        const int lane_e = lane_now(lane);
         const int lane = lane_e, l31 = lane & 31, lh = lane >> 5;
         const int piece = lane & 3, rrow = lane >> 2;
         char* wr = eb + srow(l31);
@@ -777,16 +703,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
         const int mw = tm * TBM3 + wm * MI3 * 32;                  // first output row / column of this wave
         const int nw = tn * TBN3 + wn * NJ3 * 32;
         int idx_u = -1;                                            // >= 0: the one row-vector row of this wave's 64 rows
-        if constexpr (RV) {
-            if (a.rv_mod_in == 1) {                                // idx(m) = ((m / div) * mul) % mod_out: a step function
-                int rv_div = a.rv_div;
-                asm volatile("" : "+s"(rv_div));
-                const int m0 = mw < a.M ? mw : a.M - 1, m1 = mw + 32 * MI3 - 1 < a.M ? mw + 32 * MI3 - 1 : a.M - 1;
-                const int q0 = m0 / rv_div, q1 = m1 / rv_div;
-                if (q0 == q1) idx_u = (q0 * a.rv_mul) % a.rv_mod_out;
-            }
-            idx_u = __builtin_amdgcn_readfirstlane(idx_u);
-        }
+        if constexpr (RV) idx_u = rowvec_uniform_idx<32 * MI3>(a, mw);
         // accumulators start at bias (from its LDS slot) + the wave's row of the row vector
         if (SPLIT && cph == 1) {
 #pragma unroll
@@ -796,7 +713,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
         } else {
-            const int lane_e = lane_now();
+            const int lane_e = lane_now(lane);
             const int lh_e = lane_e >> 5;
 #pragma unroll
             for (int j = 0; j < NJ3; ++j)
@@ -973,6 +890,12 @@ int igemm320_init() {
                : MOFA_ELAUNCH;
 }
 
+// can the 256x320 tile run these arguments?  (kind 7 has no kernel here)
+static bool igemm320_eligible(const mofa_igemm_args* a, int kind, int taps) {
+    if (kind == 7 || !igemm_pipe_eligible(a, kind, (long long)taps * a->Cin)) return false;
+    return (long long)(a->N + TBN3) * taps * a->Cin * 2 < 0x7ff00000LL;   // unclamped W row offsets stay below W_DEAD
+}
+
 // can a launch with these arguments emit mofa_igemm_args.stats?  (a->stats itself is not looked at)
 bool igemm320_stats_ok(const mofa_igemm_args* a) {
     if (!a || !a->x || !a->w || !a->out || a->M <= 0 || a->N <= 0 || a->Cin <= 0 || a->Cin % 64 != 0) return false;
@@ -980,11 +903,7 @@ bool igemm320_stats_ok(const mofa_igemm_args* a) {
     if (a->M % 64 != 0 || a->N % TBN3 != 0) return false;
     if (a->rowvec && (a->rv_mod_in != 1 || a->rv_div <= 0 || a->rv_div % 64 != 0)) return false;   // constant over a wave's 64 rows
     if (a->tile != 0 && a->tile != MOFA_TILE_256X320) return false;
-    const int taps = a->mode == MOFA_MODE_CONV3X3 ? (a->ksize > 0 ? a->ksize * a->ksize : 9) : (a->mode == MOFA_MODE_CONVT3 ? 3 : 1);
-    const int kind = (a->r1 ? 1 : 0) | (a->rowvec ? 4 : 0);
-    if (!igemm_pipe_eligible(a, kind, (long long)taps * a->Cin)) return false;
-    if ((long long)(a->N + TBN3) * taps * a->Cin * 2 >= 0x7ff00000LL) return false;
-    return true;
+    return igemm320_eligible(a, (a->r1 ? 1 : 0) | (a->rowvec ? 4 : 0), igemm_taps(*a));
 }
 
 // Split-K for the tiles of a partial last round.  T tiles on n_cu persistent workgroups take ceil(T / n_cu) tile times although
@@ -1012,10 +931,9 @@ int igemm320_split(long long T, int nk, int n_cu, long long ws_bytes) {
 
 // returns 0 launched, < 0 error, 1 not eligible (the caller falls back to another tile)
 int igemm320_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t stream) {
-    const int taps = a->mode == MOFA_MODE_CONV3X3 ? (a->ksize > 0 ? a->ksize * a->ksize : 9) : (a->mode == MOFA_MODE_CONVT3 ? 3 : 1);
-    if (kind == 7 || !igemm_pipe_eligible(a, kind, (long long)taps * a->Cin)) return 1;
+    const int taps = igemm_taps(*a);
+    if (!igemm320_eligible(a, kind, taps)) return 1;
     constexpr int tbn = TBN3;
-    if ((long long)(a->N + tbn) * taps * a->Cin * 2 >= 0x7ff00000LL) return 1;   // unclamped W row offsets stay below W_DEAD
     const int tilesM = cdiv(a->M, TBM3), tilesN = cdiv(a->N, tbn);
     const long long nt = (long long)tilesM * tilesN;
     if (nt > 0x7fffffffLL) return MOFA_EINVAL;
@@ -1025,9 +943,7 @@ int igemm320_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t st
     const int S = kind == 8 ? 1 : igemm320_split(nt, nk, n_cu, ws_ok ? a->workspace_bytes : 0);   // (the fix-up has no GEGLU form)
     if (a->stats && (kind > 6 || !k_igemm320_stats[kind] || (((size_t)a->stats) & 15) || !igemm320_stats_ok(a))) return MOFA_EINVAL;
     if (S == 1) {
-        int grid = (int)(nt < n_cu ? ((nt + 7) / 8) * 8 : (n_cu / 8) * 8);
-        if (grid < 8) grid = 8;
-        hipLaunchKernelGGL(a->stats ? k_igemm320_stats[kind] : k_igemm320[kind], dim3(grid), dim3(512), LDS_BYTES3, stream, *a, tilesN,
+        hipLaunchKernelGGL(a->stats ? k_igemm320_stats[kind] : k_igemm320[kind], dim3(igemm_grid(nt, n_cu)), dim3(512), LDS_BYTES3, stream, *a, tilesN,
                            (int)nt, aux);
         MOFA_CHECK_LAUNCH();
         return MOFA_OK;

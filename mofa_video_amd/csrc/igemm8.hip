@@ -51,14 +51,6 @@ constexpr int SCRATCH0 = 2 * STB, SCRATCH_WAVE = 4096;
 constexpr int LDS_BYTES = SCRATCH0 + 8 * SCRATCH_WAVE;         // 163840 = the CU's whole LDS
 constexpr int LOOKAHEAD_OPS = 8;                               // DMA instructions of the last 2 phases may be in flight
 
-// epilogue scratch images (tools/lds_bank_sim.py)
-__device__ __forceinline__ int h16_off(int r, int c8) {        // 32 rows x 64 fp16; c8 = 8-byte chunk (4 columns)
-    return r * 128 + (((c8 >> 1) ^ ((r >> 1) & 7)) << 4) + (((c8 & 1) ^ (r & 1)) << 3);
-}
-__device__ __forceinline__ int f32_off(int r, int c) {         // 32 rows x 32 fp32; c = 16-byte chunk (4 columns)
-    return r * 128 + ((c ^ (((r >> 1) & 3) | ((r & 1) << 2))) << 4);
-}
-
 struct Cursor {                     // one half-tile pair (X half h, W half h) of the persistent K-tile stream
     int local;                      // walk position of the output tile it is in
     int ikc, ksw, ky, kx;           // K tile within the tap / overall, tap coordinates (convT3: ky = tap)
@@ -96,59 +88,20 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
     // X tile row = (hr / 64) * 128 + h * 64 + hr % 64, W tile row = (hr / 32) * 64 + h * 32 + hr % 32; the 16-byte slot
     // lane % 8 of a row holds source chunk slot ^ ((row >> 1) & 7) = slot ^ (4 q + lane / 16)
     // (lane-derived values are recomputed where they are used -- per tap / per tile -- instead of living in VGPRs)
-    auto lane_now = [&]() __attribute__((always_inline)) { int l = lane; asm volatile("" : "+v"(l)); return l; };
     auto swz_bytes = [&](int l, int q) __attribute__((always_inline)) { return (((l & 7) ^ (4 * q + (l >> 4))) * 16); };
     auto x_row = [&](int h, int q, int hr0) __attribute__((always_inline)) { const int hr = hr0 + 8 * q; return (hr >> 6) * 128 + h * 64 + (hr & 63); };
     auto w_row = [&](int h, int q, int hr0) __attribute__((always_inline)) { const int hr = hr0 + 8 * q; return (hr >> 5) * 64 + h * 32 + (hr & 31); };
-    const int ks_ = a.ksize > 0 ? a.ksize : 3, dil_ = a.dil > 0 ? a.dil : 1;
-    const int org_ = a.pad == MOFA_PAD_TRAILING ? 0 : (ks_ >> 1);
-    // (single-exit lambdas: with several return statements hipcc leaves the result slots in scratch memory)
-    auto pack_geo = [&](int m) __attribute__((always_inline)) -> int {
-        int g = m;
-        if (a.mode == MOFA_MODE_CONV3X3) {
-            const int img = fdiv(m, aux.hw), rem = m - img * (a.Hout * a.Wout);
-            const int oy = fdiv(rem, aux.wout);
-            g = (img << 20) | (oy << 10) | (rem - oy * a.Wout);
-        } else if (a.mode == MOFA_MODE_CONVT3) {
-            int lo = 1, hi = 1;
-            if (a.T > 0) {
-                const int fr = fdiv(m, aux.t3hw);                  // frame index; its position within the clip of T
-                const int f = fr - fdiv(fr, aux.t3t) * a.T;
-                lo = f > 0; hi = f < a.T - 1;
-            }
-            g = m | (lo << 29) | (hi << 30);
-        }
-        return m < a.M ? g : -1;
-    };
-    const auto rsx = __builtin_amdgcn_make_buffer_rsrc((void*)aux.xbase, 0, aux.x_bytes, 0x00020000);
-    const auto rsw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, aux.w_bytes, 0x00020000);
-    auto bglds16 = [&](const decltype(rsx)& rs, unsigned voff, int soff, char* lds_wave_base) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-    };
-    auto tap_src = [&](int g, int ky, int kx, int swzb) __attribute__((always_inline)) -> unsigned {   // bytes from aux.xbase
-        int row = g;                                               // plain: the output row itself
-        bool ok = g >= 0;
-        if (a.mode == MOFA_MODE_CONV3X3) {
-            const int vy = ((g >> 10) & 1023) * a.stride + (ky - org_) * dil_;
-            const int vx = (g & 1023) * a.stride + (kx - org_) * dil_;
-            ok = ok && vy >= 0 && vx >= 0 && vy < a.Hin * a.up && vx < a.Win * a.up;
-            const int iy = (a.up == 2) ? (vy >> 1) : vy, ix = (a.up == 2) ? (vx >> 1) : vx;
-            row = ((g >> 20) * a.Hin + iy) * a.Win + ix;
-        } else if (a.mode == MOFA_MODE_CONVT3) {                   // tap ky - 1 frames away
-            ok = ok && !(ky == 0 && !((g >> 29) & 1)) && !(ky == 2 && !((g >> 30) & 1));
-            row = (g & 0x1fffffff) + (ky - 1) * a.HW + aux.row_shift;
-        }
-        const unsigned off = (unsigned)row * (unsigned)aux.ldxb + (unsigned)swzb;
-        return ok ? off : XO_INVALID;
-    };
+    const TapGeo tg(a);
+    const BufRsrc rsx = buf_rsrc(aux.xbase, aux.x_bytes), rsw = buf_rsrc(a.w, aux.w_bytes);
+    const LdsDma16 bglds16;
     auto cur_setup = [&](Cursor& c, const int h, const bool with_w) __attribute__((always_inline)) {
         // branch-free on purpose (selects on the uniform `live`): stores to the cursor's fields from two arms of an
         // if / else get merged into a store through a pointer phi, which pins those fields to scratch memory
         const bool live = c.local < walk.count;
         const int tile = walk.start + (live ? c.local : 0);
         const int tm = fdiv(tile, aux.tiles_n), tn = tile - tm * tilesN;
-        const int l = lane_now(), hr_l = 16 * wave + (l >> 3);
-        const int g0 = pack_geo(tm * TBM + x_row(h, 0, hr_l)), g1 = pack_geo(tm * TBM + x_row(h, 1, hr_l));
+        const int l = lane_now(lane), hr_l = 16 * wave + (l >> 3);
+        const int g0 = pack_geo(a, aux, tm * TBM + x_row(h, 0, hr_l)), g1 = pack_geo(a, aux, tm * TBM + x_row(h, 1, hr_l));
         c.gx0 = live ? g0 : -1;
         c.gx1 = live ? g1 : -1;
         if (with_w) {
@@ -164,9 +117,9 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
     };
     auto issue_x = [&](Cursor& c, const int h, const int bo) __attribute__((always_inline)) {
         if (c.ikc == 0) {
-            const int l = lane_now();
-            c.xo0 = tap_src(c.gx0, c.ky, c.kx, swz_bytes(l, 0));
-            c.xo1 = tap_src(c.gx1, c.ky, c.kx, swz_bytes(l, 1));
+            const int l = lane_now(lane);
+            c.xo0 = tap_src(a, aux, tg, c.gx0, c.ky, c.kx, swz_bytes(l, 0));
+            c.xo1 = tap_src(a, aux, tg, c.gx1, c.ky, c.kx, swz_bytes(l, 1));
         }
         bglds16(rsx, c.xo0, c.ikc * (BKS * 2), smem + bo + x_row(h, 0, 16 * wave) * RB);
         bglds16(rsx, c.xo1, c.ikc * (BKS * 2), smem + bo + x_row(h, 1, 16 * wave) * RB);
@@ -178,11 +131,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
         bglds16(rsw, c.wo3, c.ksw * (BKS * 2), smem + bo + SXB + w_row(1, 1, 16 * wave) * RB);
     };
     auto advance = [&](Cursor& c, const int h, const bool with_w) __attribute__((always_inline)) {
-        ++c.ksw;
-        if (++c.ikc == kpt) {
-            c.ikc = 0;
-            if (a.mode == MOFA_MODE_CONV3X3) { if (++c.kx == ks_) { c.kx = 0; ++c.ky; } } else ++c.ky;
-        }
+        tap_advance(c, a, kpt, tg.ks);
         if (c.ksw == nk) { c.local += walk.stride; cur_setup(c, h, with_w); }
     };
 
@@ -204,10 +153,10 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
     // scratch is idle during the K loop; columns beyond N read as zero through the descriptor's bounds check), so the
     // epilogue starts with LDS reads instead of a global-memory round trip.
     char* scr = smem + SCRATCH0 + wave * SCRATCH_WAVE;
-    const auto rsb = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? (unsigned)a.N * 4u : 0u, 0x00020000);
+    const BufRsrc rsb = buf_rsrc(a.bias, a.bias ? (unsigned)a.N * 4u : 0u);
     auto bias_prefetch = [&](int nw, int slot = 0) __attribute__((always_inline)) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (__attribute__((address_space(3))) void*)(scr + slot * 256), 4,
-                                                 (unsigned)(nw + lane_now()) * 4u, 0, 0, 0);
+                                                 (unsigned)(nw + lane_now(lane)) * 4u, 0, 0, 0);
     };
     // GEGLU kind (BIAS_INIT): the bias is the INITIAL VALUE of the accumulators, as in igemm320.hip -- its epilogue is bound by
     // VALU issue (about 15 instructions per output; the two bias adds were 2 of them) and does not transpose through the
@@ -299,13 +248,6 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
     };
 
     // ---- epilogue pieces -------------------------------------------------------------------------------------------------
-    auto act_apply = [&](auto ac, float v) __attribute__((always_inline)) -> float {
-        constexpr int ACT = decltype(ac)::v;
-        if constexpr (ACT == MOFA_ACT_SILU) return silu_f(v);
-        else if constexpr (ACT == MOFA_ACT_RELU) return fmaxf(v, 0.0f);
-        else if constexpr (ACT == MOFA_ACT_GELU) return gelu_erf_f(v);
-        else return v;
-    };
     // kinds without residuals (plain, row vector, GEGLU): bias / row vector / activation in the accumulator (fragment)
     // layout -- register r of accumulator tile (i, j) is row 32 i + l31, column 32 j + 8 (r >> 2) + 4 lh + (r & 3) --
     // then fp16 and a 32 x 64 fp16 transpose through the scratch; a lane stores 8 consecutive columns of one row
@@ -321,7 +263,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
         // they stay live across the K loop and get spilled to scratch (and reloaded here, latency-bound)
         // (row-vector kinds only, the ones that spilled: elsewhere the hoisted offsets fit and recomputing them costs 500-900
         // cycles per tile)
-        const int lane_e = RV ? lane_now() : lane;
+        const int lane_e = RV ? lane_now(lane) : lane;
         const int lane = lane_e, l31 = lane & 31, lh = lane >> 5;
         f16* out = (f16*)a.out;
         float saccv = a.s_acc;                                     // VGPR operand on purpose (see igemm.hip's epilogue)
@@ -409,17 +351,14 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
                             const float v = acc[i][j][4 * g + e] + (RV && !UNI ? rv[j][g][e] : bv[j][g][e]);
                             o[e] = (f16)act_apply(ac, saccv * v);
                         }
-                        *(f16x4*)(scr + h16_off(l31, 8 * j + 2 * g + lh)) = o;
+                        *(f16x4*)(scr + h16_off(l31 * 128, l31, 8 * j + 2 * g + lh)) = o;
                     }
                 if (RV && !UNI && i + 1 < MI) rv_load(i + 1, rv);
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
-                    const int row = 8 * p + (lane >> 3), blk = lane & 7;
-                    const f16x8 v = *(const f16x8*)(scr + row * 128 + ((blk ^ ((row >> 1) & 7)) << 4));
-                    const int mr = mw + 32 * i + row, n = nw + 8 * blk;
-                    f16x8 o = v;
-                    if (row & 1) o = (f16x8){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
-                    if (mr < a.M && n + 8 <= nout) *(f16x8*)(out + (size_t)mr * a.ldo + n) = o;
+                    const H16Piece r = h16_row<4 * NJ>(scr, RowLines128{}, lane, p);
+                    const int mr = mw + 32 * i + r.row, n = nw + 8 * r.blk;
+                    if (mr < a.M && n + 8 <= nout) *(f16x8*)(out + (size_t)mr * a.ldo + n) = r.v;
                 }
             }
         }
@@ -433,7 +372,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
         constexpr int REGS = (R1 ? 8 : 0) + (R2 ? 8 : 0) + (RV && !UNI ? 16 : 0);   // VGPRs of one step's loads
         constexpr int D0 = REGS <= 8 ? 8 : (REGS <= 16 ? 4 : (REGS <= 24 ? 2 : 1));
         constexpr int D = RV && UNI ? (REGS <= 8 ? 4 : 2) : (RV ? 1 : D0);   // (row-vector kinds: 16 more registers are taken)
-        const int lane_e = RV ? lane_now() : lane;                 // (recomputed per tile, see epilogue_light)
+        const int lane_e = RV ? lane_now(lane) : lane;           // (recomputed per tile, see epilogue_light)
         const int lane = lane_e, l31 = lane & 31, lh = lane >> 5;
         f16* out = (f16*)a.out;
         const f16* r1 = (const f16*)a.r1;
@@ -491,14 +430,14 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * g + e];
-                *(f32x4*)(scr + f32_off(l31, 2 * g + lh)) = v;
+                *(f32x4*)(scr + f32_off(l31 * 128, l31, 2 * g + lh)) = v;
             }
             const int n = nw + 32 * j + 8 * piece;
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
                 const int row = 16 * p + (lane >> 2);
-                const f32x4 v0 = *(const f32x4*)(scr + f32_off(row, 2 * piece));
-                const f32x4 v1 = *(const f32x4*)(scr + f32_off(row, 2 * piece + 1));
+                const f32x4 v0 = *(const f32x4*)(scr + f32_off(row * 128, row, 2 * piece));
+                const f32x4 v1 = *(const f32x4*)(scr + f32_off(row * 128, row, 2 * piece + 1));
                 f16x8 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -534,7 +473,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
                 tn2 = tile2 - fdiv(tile2, aux.tiles_n) * tilesN;
             }
             bias_prefetch(tn2 * TBN + wn * NJ * 32, bslot ^ 1);
-            const int lh_e = lane_now() >> 5;
+            const int lh_e = lane_now(lane) >> 5;
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
 #pragma unroll
@@ -570,16 +509,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
         const int mw = tm * TBM + wm * MI * 32;                    // first output row / (pre-GEGLU) column of this wave
         const int nw = tn * TBN + wn * NJ * 32;
         int idx_u = -1;                                            // >= 0: the one row-vector row of this wave's block
-        if constexpr (RV) {
-            if (a.rv_mod_in == 1) {                                // idx(m) = ((m / div) * mul) % mod_out: a step function
-                int rv_div = a.rv_div;
-                asm volatile("" : "+s"(rv_div));
-                const int m0 = mw < a.M ? mw : a.M - 1, m1 = mw + 32 * MI - 1 < a.M ? mw + 32 * MI - 1 : a.M - 1;
-                const int q0 = m0 / rv_div, q1 = m1 / rv_div;
-                if (q0 == q1) idx_u = (q0 * a.rv_mul) % a.rv_mod_out;
-            }
-            idx_u = __builtin_amdgcn_readfirstlane(idx_u);
-        }
+        if constexpr (RV) idx_u = rowvec_uniform_idx<32 * MI>(a, mw);
         if constexpr (R1 || R2) {
             if (RV && idx_u >= 0) epilogue_residual(IC<1>{}, acc, mw, nw, idx_u);
             else epilogue_residual(IC<0>{}, acc, mw, nw, 0);
@@ -642,7 +572,7 @@ int igemm8_init() {
 }
 
 int igemm8_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t stream) {
-    const int taps = a->mode == MOFA_MODE_CONV3X3 ? (a->ksize > 0 ? a->ksize * a->ksize : 9) : (a->mode == MOFA_MODE_CONVT3 ? 3 : 1);
+    const int taps = igemm_taps(*a);
     if (!igemm_pipe_eligible(a, kind, (long long)taps * a->Cin)) return 1;   // the caller falls back to a 4-wave tile
     const int tilesM = cdiv(a->M, TBM), tilesN = cdiv(a->N, TBN);
     const long long nt = (long long)tilesM * tilesN;
@@ -656,9 +586,7 @@ int igemm8_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t stre
             if (k_probe_vars[i] == s_probe_var) kern = k_probe_kern[i];
     if (s_probe_var == 64 && k_trace_kern[kind]) kern = k_trace_kern[kind];
 #endif
-    int grid = (int)(nt < n_cu ? ((nt + 7) / 8) * 8 : (n_cu / 8) * 8);
-    if (grid < 8) grid = 8;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS_BYTES, stream, *a, tilesN, (int)nt, aux);
+    hipLaunchKernelGGL(kern, dim3(igemm_grid(nt, n_cu)), dim3(512), LDS_BYTES, stream, *a, tilesN, (int)nt, aux);
     MOFA_CHECK_LAUNCH();
     return MOFA_OK;
 }

@@ -1,6 +1,7 @@
-// Pieces shared by the two implicit-GEMM translation units (igemm.hip: 4-wave tiles + the launcher; igemm8.hip: the
-// 8-wave 256x256 phase-pipelined kernel): implicit-GEMM row geometry, the XCD-aware persistent tile walk, the LDS-DMA
-// primitive and the counted waits.
+// Pieces shared by the three implicit-GEMM translation units (igemm.hip: 4-wave tiles + the launcher; igemm8.hip and
+// igemm320.hip: the 8-wave phase-pipelined 256x256 and 256x320 kernels, which share more in igemm_pipe.h): the tap count,
+// the XCD-aware persistent tile walk and its grid size, the epilogue kind bits, the counted waits and the 8-wave launchers'
+// prototypes; for the 4-wave kernels also the two-register row geometry, its tap source and the pointer LDS-DMA primitive.
 #pragma once
 #include "common.h"
 
@@ -57,7 +58,7 @@ __device__ __forceinline__ const f16* x_src(const mofa_igemm_args& a, const RowG
     }
 }
 
-__device__ __forceinline__ int igemm_taps(const mofa_igemm_args& a) {
+__host__ __device__ __forceinline__ int igemm_taps(const mofa_igemm_args& a) {
     return (a.mode == MOFA_MODE_CONV3X3) ? (a.ksize > 0 ? a.ksize * a.ksize : 9) : (a.mode == MOFA_MODE_CONVT3 ? 3 : 1);
 }
 
@@ -75,6 +76,11 @@ struct TileWalk {
         stride = gridDim.x >> 3;
     }
 };
+// its grid: one workgroup per tile up to `slots` resident workgroups, a multiple of 8 (equal shares per XCD), at least 8
+static inline int igemm_grid(long long ntiles, int slots) {
+    const int grid = (int)(ntiles < slots ? ((ntiles + 7) / 8) * 8 : (slots / 8) * 8);
+    return grid < 8 ? 8 : grid;
+}
 
 #define EPI_R1 1
 #define EPI_R2 2
