@@ -254,7 +254,7 @@ def _into(out, y):
 
 def attn_spatial(q, k, v, nframes, heads, S, head_dim=64, scale=None, out=None, prescaled=False, query_blocks=0):
     """query_blocks picks the workgroup height on the real side and leaves the result's meaning unchanged: ignored here"""
-    assert head_dim in (64, 128) and S % 8 == 0
+    assert head_dim in (64, 128)
     scale = head_dim ** -0.5 if scale is None else scale
     if prescaled:                       # q holds Q * head_dim^-0.5 * log2(e): softmax in base 2
         scale = 0.6931471805599453
