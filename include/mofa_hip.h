@@ -46,6 +46,12 @@ int mofa_version(void);
  * in fp32 and the sum is rounded once more -- the reference's fp16 modules produce the layer's output in fp16 and then add --;
  * without residuals there is one rounding.  Every tile kernel rounds this way, so the tile choice never changes the bits of an
  * exactly representable sum (tests/test_igemm_tiles_gpu.py::test_all_tiles_round_residual_adds_alike).
+ * Geometry limits of MOFA_MODE_CONV3X3 (rows are packed into registers; beyond a limit the launcher returns MOFA_EINVAL for a
+ * forced tile and never truncates): the 4-wave tiles (128x128, 192x128) take Hout, Wout <= 65535 -- (oy << 16) | ox as an
+ * unsigned word -- and any image count; the 8-wave tiles (256x256, 256x320) take Hout, Wout <= 1024 and at most 2047 images
+ * -- img << 20 | oy << 10 | ox -- and need input rows * ldx * 2 bytes below 4 GB - 64 KB (32-bit buffer offsets).  With
+ * MOFA_TILE_AUTO a call beyond the 8-wave limits runs on a 4-wave tile; Hout or Wout > 65535 is MOFA_EINVAL for every tile.
+ * tests/test_igemm_conv_edges_gpu.py runs the last value of every field, and the first refused one, on every tile.
  * Replaces every nn.Linear / nn.Conv2d(1x1, 3x3 s1/s2, nearest-2x + 3x3) / nn.Conv3d((3,1,1))
  * the reference reaches through diffusers blocks (ResnetBlock2D, TemporalResnetBlock,
  * Downsample2D, Upsample2D, Attention.to_q/k/v/out, FeedForward; built at

@@ -7,7 +7,8 @@
 
 struct RowGeo {   // two registers per DMA row group
     int a;        // plain / convT3: global output row m; conv: image index; -1 when the row is beyond M
-    int b;        // conv: (oy << 16) | ox of the output pixel; convT3: frame index within its clip
+    int b;        // conv: (oy << 16) | ox of the output pixel, an UNSIGNED word (oy, ox <= 65535: oy >= 32768 sets bit 31);
+                  // convT3: frame index within its clip
 };
 
 // source of out-of-image taps / rows beyond M (one copy per translation unit; never written)
@@ -26,7 +27,7 @@ __device__ __forceinline__ RowGeo make_geo(const mofa_igemm_args& a, int m) {
         const int img = m / hw, rem = m - img * hw;
         const int oy = rem / wout;
         g.a = (m < a.M) ? img : -1;
-        g.b = (oy << 16) | (rem - oy * wout);
+        g.b = (int)(((unsigned)oy << 16) | (unsigned)(rem - oy * wout));
     } else if (a.mode == MOFA_MODE_CONVT3) {
         int HW = a.HW, T = a.T;
         asm volatile("" : "+s"(HW), "+s"(T));
@@ -45,7 +46,7 @@ __device__ __forceinline__ const f16* x_src(const mofa_igemm_args& a, const RowG
         const int dil = a.dil > 0 ? a.dil : 1;
         const int ky = tap / ks, kx = tap - ky * ks;
         const int org = a.pad == MOFA_PAD_TRAILING ? 0 : (ks >> 1);
-        const int vy = (g.b >> 16) * a.stride + (ky - org) * dil;
+        const int vy = (int)((unsigned)g.b >> 16) * a.stride + (ky - org) * dil;   // (logical shift: see RowGeo::b)
         const int vx = (g.b & 0xffff) * a.stride + (kx - org) * dil;
         if (vy < 0 || vx < 0 || vy >= a.Hin * a.up || vx >= a.Win * a.up) return nullptr;
         const int iy = (a.up == 2) ? (vy >> 1) : vy;

@@ -135,3 +135,57 @@ def test_tracks_to_controlnet_flow_end_to_end(models):
     e = rel_l2(got, ref)
     print(f"tracks -> controlnet_flow: rel-L2 {e:.3e}")
     assert tuple(got.shape) == (1, T - 1, 2, H, W) and e < 2e-2
+
+
+@pytest.fixture(scope="module")
+def cmp_reference(models):
+    """the oracle's logits and flow of one input, computed once for the forced-tile cases"""
+    o, _ = models
+    image, sparse, mask = cmp_inputs(2, 128, 160, seed=5)
+    with torch.no_grad():
+        ref_logits = o.model(image * 2 - 1, torch.cat([sparse, mask], dim=1))
+    return image, sparse, mask, ref_logits, o.run(image, sparse, mask)
+
+
+@pytest.mark.parametrize("tile", ["192x128", "256x256", "256x320"])
+def test_cmp_same_result_on_every_forced_tile(models, cmp_reference, tile):
+    """the CMP forward with every implicit-GEMM launch forced onto one tile (ineligible launches keep the default): the
+    pattern of test_config1_gpu.py::test_config1_same_result_on_every_forced_tile.  At this size the cost model puts every
+    layer on the 128x128 tile, at production size the 3x3 dilation-2 / dilation-4 stages, the 7x7 stride-2 stem and the 5x5
+    stride-2 sparse stem go to an 8-wave tile: they must have ACCEPTED the two 8-wave tiles here (plain + ReLU epilogues,
+    16-byte rows, N = 256 / 512 / 64 / 16), so that tap_src with ksize != 3 and dil != 1 is compared inside the model"""
+    from mofa_video_amd import lib, ops
+    _, hm = models
+    image, sparse, mask, ref_logits, ref_flow = cmp_reference
+    forced = {"192x128": lib.TILE_192X128, "256x256": lib.TILE_256X256, "256x320": lib.TILE_256X320}[tile]
+    orig = ops.igemm
+    took = {"dil2": 0, "dil4": 0, "k7": 0, "k5": 0, "forced": 0, "default": 0}
+
+    def igemm_forced(*a, **kw):
+        if kw.pop("tile", None) is None:
+            try:
+                y = orig(*a, tile=forced, **kw)
+            except lib.MofaHipError:                                    # MOFA_EINVAL: this launch is not eligible for the tile
+                pass
+            else:
+                g = kw.get("geom") or ops.PLAIN
+                took["forced"] += 1
+                if g.mode == lib.MODE_CONV3X3:
+                    for key, hit in (("dil2", g.dil == 2), ("dil4", g.dil == 4), ("k7", g.ksize == 7), ("k5", g.ksize == 5)):
+                        took[key] += int(hit)
+                return y
+        took["default"] += 1
+        return orig(*a, **kw)
+    ops.igemm = igemm_forced
+    try:
+        logits, h, w = hm.model.forward((image * 2 - 1).to(DEV), torch.cat([sparse, mask], dim=1).to(DEV))
+        got = hm.run(image.to(DEV), sparse.to(DEV), mask.to(DEV)).cpu()
+    finally:
+        ops.igemm = orig
+    e, ef = rel_l2(_untok(logits, 2, 198, h, w), ref_logits), rel_l2(got, ref_flow)
+    print(f"CMP, every igemm on the {tile} tile: logits rel-L2 {e:.3e}, flow rel-L2 {ef:.3e}; launches {took}")
+    assert (h, w) == (64, 80) and e < 2e-2
+    assert tuple(got.shape) == tuple(ref_flow.shape) and ef < 2e-2
+    assert took["forced"] > took["default"]
+    if tile != "192x128":
+        assert min(took["dil2"], took["dil4"], took["k7"], took["k5"]) >= 1, took
