@@ -441,6 +441,18 @@ int64_t mofa_flow_to_image_ws_bytes(int H, int W);
 int mofa_flow_to_image_u8(const float* flow_hw2, unsigned char* out_hw3, int H, int W, void* workspace,
                           mofa_stream_t stream);
 
+/* ---- landmark pose images (the `landmarks` argument of the Keypoint / Hybrid pipelines) ---------------------
+ * Replaces draw_landmarks (MOFA-Video-Keypoint/utils/utils.py:26-46: the 15 polylines of a 68-point face, 63 segments,
+ * cv2.line(thickness=2) on a draw_size x draw_size float64 canvas) + cv2.resize to the clip size + / 255
+ * (mofa_keypoint.py:299-316), bit-equal to mofa_video_amd/landmarks.py's restatement of them.
+ * pts: device int32 [N][68][2] (x, y), landmark coordinates already scaled to the draw_size canvas and truncated toward
+ * zero (as draw_landmarks' int() does), each within +-32767: a segment with an end point beyond that is not drawn.
+ * out: device fp32 [N][3][H][W], values in [0, 1].
+ * workspace: device, N * draw_size * draw_size * 4 bytes, 16-byte aligned (the int32 segment-index canvases; the call
+ * clears them itself).  draw_size <= 4096; H * W < 2^31. */
+int mofa_pose_images_f32(const int32_t* pts, float* out, void* workspace, int N, int H, int W, int draw_size,
+                         mofa_stream_t stream);
+
 /* ---- image conditioning front end (the step before the loop) ------------------------------------------------
  * _resize_with_antialiasing (MOFA-Video-Traj/pipeline/pipeline.py:531-562) = separable Gaussian blur with reflect
  * padding (_gaussian_blur2d :632-645, _filter2d :587-610; x pass then y pass) + F.interpolate(bicubic, align_corners=True).

@@ -274,12 +274,30 @@ def resize_linear(img, width, height):
     return rows[y0] * by0[:, None, None] + rows[y1] * by1[:, None, None]
 
 
-def pose_images(landmarks, height, width, draw_size=320):
+MAX_DEVICE_COORD = 32767   # |scaled coordinate| the device rasteriser takes (bounds the scanline walk of one segment)
+
+
+def pose_images(landmarks, height, width, draw_size=320, device=None):
     """MOFA-Video-Keypoint/mofa_keypoint.py:299-316: landmarks [N, 68, 2] in pixel coordinates of the height x width
     frame -> pose images fp32 [1, N, 3, height, width] in [0, 1] (drawn at 320 x 320 "because training uses 320 x 320",
-    then resized), the ``landmarks`` argument of the Keypoint / Hybrid pipelines"""
+    then resized), the ``landmarks`` argument of the Keypoint / Hybrid pipelines.
+
+    ``device=None``: drawn and resized on the host, returned on the CPU.  With a device only the scaling and the truncation
+    toward zero (``draw_landmarks``' ``int()``) happen here; the N * 68 * 2 int32 coordinates are uploaded and
+    ``ops.pose_images`` (csrc/landmarks.hip) rasterises and resizes there, bit-equal to the host path's ``.to(device)``."""
     lm = np.array(landmarks, dtype=np.float64).copy()
     lm[:, :, 0] = lm[:, :, 0] / width * draw_size
     lm[:, :, 1] = lm[:, :, 1] / height * draw_size
+    if device is not None:
+        from . import ops
+        if lm.ndim != 3 or lm.shape[1:] != (68, 2):
+            raise ValueError(f"landmarks [N, 68, 2] expected, got {lm.shape}")
+        if not np.isfinite(lm).all():
+            raise ValueError("non-finite landmark coordinate")
+        pts = np.trunc(lm)
+        if (np.abs(pts) > MAX_DEVICE_COORD).any():
+            raise ValueError(f"scaled landmark coordinate beyond +-{MAX_DEVICE_COORD}: the device rasteriser does not take it")
+        pts = torch.from_numpy(pts.astype(np.int32)).to(device)
+        return ops.pose_images(pts, height, width, draw_size).unsqueeze(0)
     imgs = np.stack([resize_linear(draw_landmarks(lm[i], draw_size, draw_size), width, height) for i in range(lm.shape[0])])
     return (torch.from_numpy(imgs).permute(0, 3, 1, 2).float() / 255.0).unsqueeze(0)

@@ -144,6 +144,7 @@ PROTOTYPES = {
     "mofa_frames_postprocess_f32": [_P, _P, _I, _I, _I, _I, _P],
     "mofa_flow_to_image_ws_bytes": [_I, _I],
     "mofa_flow_to_image_u8": [_P, _P, _I, _I, _P, _P],
+    "mofa_pose_images_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
 }
 _RESTYPE = {"mofa_softsplat_ws_bytes": C.c_int64, "mofa_flow_to_image_ws_bytes": C.c_int64}
 

@@ -860,6 +860,33 @@ def flow_to_image(flow_hw2):
     return out
 
 
+# ---- landmark pose images -------------------------------------------------------------------
+POSE_MAX_COORD = 32767         # |scaled landmark coordinate| the rasteriser draws (bounds one lane's scanline walk)
+
+
+def pose_images(pts_i32, H, W, draw_size, out=None, workspace=None):
+    """int32 landmark coordinates [N,68,2] (x, y) on the draw_size canvas -> fp32 pose images [N,3,H,W] in [0,1]
+    (landmarks.draw_landmarks + resize_linear + / 255, bit-equal).  workspace: int32 [>= N*draw_size*draw_size] to reuse
+    across calls (the launch clears it); allocated when None."""
+    lib = L.load()
+    _chk(pts_i32, torch.int32)
+    assert pts_i32.dim() == 3 and tuple(pts_i32.shape[1:]) == (68, 2), tuple(pts_i32.shape)
+    N = pts_i32.shape[0]
+    pts_i32 = pts_i32.contiguous()
+    if out is None:
+        out = torch.empty((N, 3, H, W), dtype=F32, device=pts_i32.device)
+    _chk(out, F32)
+    assert tuple(out.shape) == (N, 3, H, W) and out.is_contiguous()
+    ws = workspace
+    if ws is None:
+        ws = torch.empty((N * draw_size * draw_size,), dtype=torch.int32, device=pts_i32.device)
+    _chk(ws, torch.int32)
+    assert ws.is_contiguous() and ws.numel() >= N * draw_size * draw_size
+    L.check(lib.mofa_pose_images_f32(L.ptr(pts_i32), L.ptr(out), L.ptr(ws), N, H, W, draw_size, L.stream_ptr()),
+            "mofa_pose_images_f32")
+    return out
+
+
 # ---- CMP sparse-to-dense motion encoder pieces (SURVEY N1) ----------------------------------------------
 def pool2d(x, nimg, H, W, C, k, stride, pad=0, mode="max", out=None):
     """token-major fp16 [nimg*H*W, ld>=C] -> [nimg*Ho*Wo, ld_out]; nn.MaxPool2d / nn.AvgPool2d semantics."""
