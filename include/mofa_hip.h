@@ -453,6 +453,35 @@ int mofa_flow_to_image_u8(const float* flow_hw2, unsigned char* out_hw3, int H, 
 int mofa_pose_images_f32(const int32_t* pts, float* out, void* workspace, int N, int H, int W, int draw_size,
                          mofa_stream_t stream);
 
+/* ---- control signals: sparse CMP input from points, controlnet_flow from CMP's output ------------------------
+ * mofa_sparse_points_f32: K points per frame -> the dense input of the CMP encoder, out fp32 [n][4][H][W] = dx, dy, mask,
+ * mask.  pos: device int32 [K][2] (row, col), shared by all n frames; val: device fp32 [n][K][2], (dx, dy) of point k in
+ * frame i.  The launch clears `out` itself (a memset on the stream, ordered before the point writes); K = 0 with
+ * pos = val = NULL is valid and only clears.  Every pixel has one writing thread, chosen by the point order alone: no
+ * atomics, bit-identical repeat launches.
+ *   MOFA_SPARSE_ADD (get_sparseflow_and_mask_forward, MOFA-Video-Traj/run_gradio.py:61-86): the pixel of point k gets the sum
+ *     of val[i][k'] over all k' on the same pixel, added in ascending k', and both mask channels their number.  Positions
+ *     must lie in [0,H) x [0,W).  They are device memory, which the launcher cannot inspect: the caller checks them
+ *     (mofa_video_amd/ops.py::sparse_points raises ValueError on the host); a point off the canvas is never written and
+ *     never counted.  The sums are exact while |sum| < 2^24 for integer-valued val.
+ *   MOFA_SPARSE_LAST (sample_optical_flow, MOFA-Video-Keypoint/utils/utils.py:81-103): positions are clipped to [0,H-1] /
+ *     [0,W-1]; the point with the highest k on a pixel wins, its val is copied bit for bit (NaN included), masks are 1.
+ * Limits: K <= 4096, n <= 65535, H * W < 2^31; beyond them, for NULL out, negative sizes or an unknown mode: MOFA_EINVAL. */
+enum { MOFA_SPARSE_ADD = 0, MOFA_SPARSE_LAST = 1 };
+int mofa_sparse_points_f32(const int* pos, const float* val, int K, int n, int H, int W, int mode, float* out,
+                           mofa_stream_t stream);
+/* mofa_flow_finish_f32: the tail of get_flow (run_gradio.py:236-277: brush multiply, nearest resize, rescale) and
+ * merge_inmask_outmask (:290-330) in one pass.  flow_in / flow_out: device fp32 [n][2][hs][ws] or NULL (= zeros: a group
+ * without tracks); brush: device uint8 [hs][ws] or NULL, applies to flow_in only; out: device fp32 [n][2][H][W].
+ * Per output pixel: src = the index of mofa_resize_nearest_f32; a = flow_in[src] * ((float)brush[src] / 255.0f) (no multiply
+ * without a brush); if (H, W) != (hs, ws), a.x and b.x are multiplied by (float)((double)W / ws), a.y and b.y by
+ * (float)((double)H / hs); out = (a.x != 0 && a.y != 0) ? a : b.  Every operation is rounded on its own.  -0.0 counts as
+ * zero, NaN as non-zero and is kept.  A flow that has no merge partner (Keypoint) goes in as flow_out with flow_in = NULL: it
+ * is resized and rescaled only -- as flow_in its pixels with one zero component would lose the other.  16-byte accesses are used where pointers and rows are 16-byte aligned, scalar ones
+ * elsewhere: no alignment is required.  H * W and hs * ws < 2^31, n * H * ceil(W / 4) < 2^39. */
+int mofa_flow_finish_f32(const float* flow_in, const float* flow_out, const unsigned char* brush, int n, int hs, int ws, int H,
+                         int W, float* out, mofa_stream_t stream);
+
 /* ---- image conditioning front end (the step before the loop) ------------------------------------------------
  * _resize_with_antialiasing (MOFA-Video-Traj/pipeline/pipeline.py:531-562) = separable Gaussian blur with reflect
  * padding (_gaussian_blur2d :632-645, _filter2d :587-610; x pass then y pass) + F.interpolate(bicubic, align_corners=True).

@@ -1,5 +1,6 @@
 // HBM-bound element-wise / data-movement kernels (16-byte vector accesses along the channel axis).
 #include "common.h"
+#include "control_points.h"        // nearest_src, shared with csrc/control.hip
 
 static inline int ew_blocks(long long n) {
     long long nb = (n + 255) / 256;
@@ -329,9 +330,7 @@ __global__ void resize_nearest_kernel(const float* __restrict__ x, float* __rest
         const long long r = i / w;
         const int oy = (int)(r % h);
         const long long plane = r / h;
-        int iy = (int)floorf((float)oy * sy), ix = (int)floorf((float)ox * sx);
-        iy = iy < H - 1 ? iy : H - 1;
-        ix = ix < W - 1 ? ix : W - 1;
+        const int iy = nearest_src(oy, sy, H), ix = nearest_src(ox, sx, W);
         y[i] = x[(plane * H + iy) * W + ix];
     }
 }

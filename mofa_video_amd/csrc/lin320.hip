@@ -138,8 +138,14 @@ __global__ __launch_bounds__(512, 2) void lin320_kernel(const mofa_lin320_args a
         if constexpr (RV) rvrow = a.rowvec + (size_t)(((mr / a.rv_div) * a.rv_mul + (mr % a.rv_mod_in)) % a.rv_mod_out) * a.N;
         // row-contiguous layout of the stores / residual loads: lane j <-> row (j >> 3) + 8 i of the wave's 32, columns 8 (j & 7) ..
         const int mw = tile * 256 + wave * 32;
-        const int mj = mw + (lane >> 3) < a.M ? mw + (lane >> 3) : 0;       // (rows beyond M: loads from row 0, stores masked)
-        const f16* rbase = R1 ? rg + (size_t)mj * a.ldr1 + 8 * (lane & 7) : nullptr;
+        // (rows beyond M: loads from row 0, stores masked.  Each of the lane's four rows is clamped on its own: in the wave that
+        // straddles M the first row can lie below M and rows + 8, + 16, + 24 beyond the residual's last row)
+        const f16* rrow[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int mj = mw + (lane >> 3) + 8 * i;
+            rrow[i] = R1 ? rg + (size_t)(mj < a.M ? mj : 0) * a.ldr1 + 8 * (lane & 7) : nullptr;
+        }
         const unsigned ldo2 = (unsigned)a.ldo * 2u;
         const unsigned obyte = (unsigned)(mw + (lane >> 3)) * ldo2 + 16u * (unsigned)(lane & 7);   // (unclamped: see the stores)
 
@@ -152,7 +158,7 @@ __global__ __launch_bounds__(512, 2) void lin320_kernel(const mofa_lin320_args a
             f16x8 rp[4];
             if constexpr (R1) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) rp[i] = *(const f16x8*)(rbase + (size_t)(8 * i) * a.ldr1 + 64 * c);
+                for (int i = 0; i < 4; ++i) rp[i] = *(const f16x8*)(rrow[i] + 64 * c);
             }
             if (c == nchunk - 1 && tile + (int)gridDim.x < ntiles) {
                 const int m2 = (tile + (int)gridDim.x) * 256 + wave * 32 + l31;

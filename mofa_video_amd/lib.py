@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("MOFA_HIP_LIB") or os.path.join(_HERE, "libmofa_hip.so
 MODE_PLAIN, MODE_CONV3X3, MODE_CONVT3 = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_GEGLU_PAIR, ACT_RELU, ACT_GELU = 0, 1, 2, 3, 4
 PAD_SAME, PAD_TRAILING = 0, 1
+SPARSE_ADD, SPARSE_LAST = 0, 1
 TILE_AUTO, TILE_128X128, TILE_192X128, TILE_256X256, TILE_256X320 = 0, 2, 4, 5, 6
 
 
@@ -145,6 +146,8 @@ PROTOTYPES = {
     "mofa_flow_to_image_ws_bytes": [_I, _I],
     "mofa_flow_to_image_u8": [_P, _P, _I, _I, _P, _P],
     "mofa_pose_images_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "mofa_sparse_points_f32": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "mofa_flow_finish_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
 }
 _RESTYPE = {"mofa_softsplat_ws_bytes": C.c_int64, "mofa_flow_to_image_ws_bytes": C.c_int64}
 

@@ -887,6 +887,65 @@ def pose_images(pts_i32, H, W, draw_size, out=None, workspace=None):
     return out
 
 
+# ---- control signals on the device ----------------------------------------------------------
+SPARSE_MAX_POINTS = 4096       # K of one mofa_sparse_points_f32 launch
+
+
+def sparse_points(pos_i32, val_f32, H, W, mode, out=None):
+    """int32 positions [K,2] (row, col) + fp32 values [n,K,2] (dx, dy) -> the CMP encoder's dense input fp32 [n,4,H,W]
+    (dx, dy, mask, mask); the launch clears ``out`` itself.  ``lib.SPARSE_ADD``: points on one pixel add up in ascending
+    order, the masks count them; a position outside the canvas raises ValueError (the host path wraps negative indices
+    the numpy way and raises IndexError beyond the canvas -- this path refuses both).  ``lib.SPARSE_LAST``: positions are
+    clipped onto the canvas, the last point of a pixel wins, its value is copied bit for bit.
+    ``pos_i32`` may be a host tensor (it is checked there and uploaded: a few KB) or a device tensor (checking it costs a
+    read-back); ``val_f32`` decides the device."""
+    assert mode in (L.SPARSE_ADD, L.SPARSE_LAST), mode
+    assert pos_i32.dtype == torch.int32 and pos_i32.dim() == 2 and pos_i32.shape[1] == 2, (pos_i32.dtype, tuple(pos_i32.shape))
+    K = pos_i32.shape[0]
+    assert val_f32.dim() == 3 and tuple(val_f32.shape[1:]) == (K, 2), (tuple(val_f32.shape), K)
+    if K > SPARSE_MAX_POINTS:
+        raise ValueError(f"{K} points in one launch; at most {SPARSE_MAX_POINTS}")
+    if mode == L.SPARSE_ADD and K:
+        p = pos_i32.cpu()
+        if bool(((p < 0) | (p >= torch.tensor([H, W]))).any()):
+            raise ValueError(f"a start position lies outside the {H} x {W} canvas")
+    lib = L.load()
+    _chk(val_f32, F32)
+    n = val_f32.shape[0]
+    pos_i32, val_f32 = pos_i32.to(val_f32.device).contiguous(), val_f32.contiguous()
+    if out is None:
+        out = torch.empty((n, 4, H, W), dtype=F32, device=val_f32.device)
+    _chk(out, F32)
+    assert tuple(out.shape) == (n, 4, H, W) and out.is_contiguous()
+    L.check(lib.mofa_sparse_points_f32(L.ptr(pos_i32) if K else None, L.ptr(val_f32) if K else None, K, n, H, W, mode, L.ptr(out),
+                                       L.stream_ptr()), "mofa_sparse_points_f32")
+    return out
+
+
+def flow_finish(flow_in, flow_out, brush, H, W, out=None):
+    """fp32 [n,2,hs,ws] in-brush / out-of-brush CMP flows (either may be None = zeros) + uint8 brush [hs,ws] or None ->
+    controlnet_flow fp32 [n,2,H,W]: brush multiply of ``flow_in``, nearest resize, rescale and merge_inmask_outmask in one
+    pass, bit-equal to cmp.get_flow's tail + control.merge_inmask_outmask."""
+    lib = L.load()
+    ref = flow_in if flow_in is not None else flow_out
+    assert ref is not None, "pass at least one flow"
+    n, _, hs, ws = ref.shape
+    for f in (flow_in, flow_out):
+        if f is not None:
+            _chk(f, F32)
+            assert tuple(f.shape) == (n, 2, hs, ws) and f.is_contiguous(), tuple(f.shape)
+    if brush is not None:
+        _chk(brush, torch.uint8)
+        assert tuple(brush.shape) == (hs, ws) and brush.is_contiguous(), tuple(brush.shape)
+    if out is None:
+        out = torch.empty((n, 2, H, W), dtype=F32, device=ref.device)
+    _chk(out, F32)
+    assert tuple(out.shape) == (n, 2, H, W) and out.is_contiguous()
+    L.check(lib.mofa_flow_finish_f32(L.ptr(flow_in), L.ptr(flow_out), L.ptr(brush), n, hs, ws, H, W, L.ptr(out), L.stream_ptr()),
+            "mofa_flow_finish_f32")
+    return out
+
+
 # ---- CMP sparse-to-dense motion encoder pieces (SURVEY N1) ----------------------------------------------
 def pool2d(x, nimg, H, W, C, k, stride, pad=0, mode="max", out=None):
     """token-major fp16 [nimg*H*W, ld>=C] -> [nimg*Ho*Wo, ld_out]; nn.MaxPool2d / nn.AvgPool2d semantics."""
