@@ -292,7 +292,8 @@ int mofa_axpby_f16(const void* x, void* y, int M, int C, int ldx, int ldy, float
  * straight into its column slice of the decoder's concat buffer (unet_spatio_temporal_condition_controlnet.py:447-459, :478-483) */
 int mofa_axpby_out_f16(const void* x, const void* y, void* out, int M, int C, int ldx, int ldy, int ldo, float a, float b,
                        mofa_stream_t stream);
-/* out[m][j] = x[m][j] * gelu(x[m][Ch + j]), j < Ch  (diffusers GEGLU, erf gelu) */
+/* out[m][j] = x[m][j] * gelu(x[m][Ch + j]), j < Ch  (diffusers GEGLU, erf gelu).  gelu(g) = g * erfc(-g / sqrt2) / 2 with
+ * fp32 relative accuracy in both tails (the fused MOFA_ACT_GEGLU_PAIR epilogue uses a clamped polynomial, 5e-5 absolute) */
 int mofa_geglu_f16(const void* x, void* out, int M, int Ch, int ldx, int ldo, mofa_stream_t stream);
 /* strided 2-D copy of a column block: dst[m][0..C) = src[m][0..C); C % 8 == 0 */
 int mofa_copy2d_f16(const void* src, void* dst, int M, int C, int lds, int ldd, mofa_stream_t stream);
@@ -496,7 +497,10 @@ int mofa_patchify_f16(const float* x, void* out, int nimg, int C, int H, int W, 
 
 /* ---- CMP sparse-to-dense motion encoder, non-convolution pieces (the step before the path) -----------------
  * Token-major fp16 maps [nimg*H*W][ld].  pool2d: nn.MaxPool2d (mode 0, padding ignored) / nn.AvgPool2d (mode 1)
- * (Traj/models/cmp/models/backbone/resnet.py:108, modules/shallownet.py:16-21, modules/decoder.py:115-139). */
+ * (Traj/models/cmp/models/backbone/resnet.py:108, modules/shallownet.py:16-21, modules/decoder.py:115-139).
+ * Output size floor((Hin + 2*pad - k) / stride) + 1 per axis.  As in torch the window must fit into the padded map and the
+ * padding is at most half a window: k > Hin + 2*pad, k > Win + 2*pad or 2*pad > k return MOFA_EINVAL (so the numerator is
+ * never negative and every window holds at least one pixel of the map); mode 1 takes pad == 0 only; C, ldx, ldo % 8 == 0. */
 int mofa_pool2d_f16(const void* x, void* out, int nimg, int Hin, int Win, int C, int ldx, int ldo, int k, int stride, int pad,
                     int mode, mofa_stream_t stream);
 /* F.interpolate(mode="bilinear", align_corners=True): token-major fp16 maps (modules/decoder.py:192-211) and fp32

@@ -100,6 +100,7 @@ class CMP:
         (198 valid columns), and (H/2, W/2).  modules/cmp.py:27-37."""
         n, _, H, W = image.shape
         assert H % 8 == 0 and W % 8 == 0
+        assert H >= 64 and W >= 64, "decoder8 pools the 1/8 map with an 8 x 8 window: smaller images have no output pixel"
         # --- image encoder (resnet.py:152-166)
         x = ops.nchw_to_tokens(image.to(self.device, torch.float32), ld=64)
         conv1, H2, W2 = self.conv1(x, n, H, W)                                   # 1/2, 64 ch

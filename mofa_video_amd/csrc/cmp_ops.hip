@@ -49,8 +49,11 @@ extern "C" int mofa_pool2d_f16(const void* x, void* out, int nimg, int Hin, int 
     if (!x || !out || nimg <= 0 || Hin <= 0 || Win <= 0 || C <= 0 || C % 8 || ldx % 8 || ldo % 8 || k <= 0 || stride <= 0 ||
         pad < 0 || mode < 0 || mode > 1 || (mode == 1 && pad != 0))
         return MOFA_EINVAL;
+    // torch's rule.  A window larger than the padded map has no output pixel: C's truncating division below would turn the
+    // negative numerator into quotient 0 for stride >= 2 and launch one row the caller (flooring) did not allocate.  With
+    // 2 * pad > k a window can lie wholly in the padding and its maximum would be -inf.
+    if (k > Hin + 2 * pad || k > Win + 2 * pad || 2 * pad > k) return MOFA_EINVAL;
     const int Hout = (Hin + 2 * pad - k) / stride + 1, Wout = (Win + 2 * pad - k) / stride + 1;
-    if (Hout <= 0 || Wout <= 0) return MOFA_EINVAL;
     const long long total = (long long)nimg * Hout * Wout * (C / 8);
     hipLaunchKernelGGL(pool2d_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const f16*)x, (f16*)out, total,
                        Hin, Win, Hout, Wout, C / 8, ldx, ldo, k, stride, pad, mode);

@@ -54,7 +54,12 @@ extern "C" int mofa_axpby_out_f16(const void* x, const void* y, void* out, int M
     return MOFA_OK;
 }
 
-// out[m][j] = x[m][j] * gelu(x[m][Ch + j])
+// out[m][j] = x[m][j] * gelu(x[m][Ch + j]).  This stand-alone pass is bound by HBM, so it takes gelu(g) = g * erfc(-g / sqrt2) / 2
+// from the library's erfcf (relative accuracy in both tails: a gate of -4 gives g * 3.2e-5, a saturated one gives g or -0
+// exactly) rather than gelu_erf_f, the clamped polynomial the VALU-bound GEGLU epilogue of the implicit GEMM uses (absolute
+// error 5e-5: 17 x the product's own rounding at g = -4).
+__device__ __forceinline__ float gelu_erfc_f(float g) { return g * (0.5f * erfcf(g * -0.70710678118654752f)); }
+
 __global__ __launch_bounds__(256) void geglu_kernel(const f16* __restrict__ x, f16* __restrict__ out, long long nvec, int CV,
                                                     int Ch, int ldx, int ldo) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
@@ -64,7 +69,7 @@ __global__ __launch_bounds__(256) void geglu_kernel(const f16* __restrict__ x, f
         const f16x8 g = *(const f16x8*)(x + (size_t)row * ldx + Ch + cv * 8);
         f16x8 o;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (f16)((float)v[e] * gelu_erf_f((float)g[e]));
+        for (int e = 0; e < 8; ++e) o[e] = (f16)((float)v[e] * gelu_erfc_f((float)g[e]));
         *(f16x8*)(out + (size_t)row * ldo + cv * 8) = o;
     }
 }

@@ -951,6 +951,8 @@ def pool2d(x, nimg, H, W, C, k, stride, pad=0, mode="max", out=None):
     """token-major fp16 [nimg*H*W, ld>=C] -> [nimg*Ho*Wo, ld_out]; nn.MaxPool2d / nn.AvgPool2d semantics."""
     lib = L.load()
     _chk(x, F16)
+    if k <= 0 or stride <= 0 or pad < 0 or k > H + 2 * pad or k > W + 2 * pad or 2 * pad > k:
+        raise ValueError(f"pool2d: window {k} (stride {stride}, pad {pad}) does not fit a {H} x {W} map, or pad > k / 2")
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     if out is None:
         out = torch.empty((nimg * Ho * Wo, C), dtype=F16, device=x.device)

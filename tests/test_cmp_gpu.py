@@ -18,6 +18,10 @@ def _tok(x):                       # [n,C,H,W] fp32 -> token-major fp16 on the d
     return x.permute(0, 2, 3, 1).reshape(n * h * w, c).half().to(DEV).contiguous()
 
 
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
 def _untok(t, n, c, h, w):
     return t.float().cpu().reshape(n, h, w, -1)[..., :c].permute(0, 3, 1, 2)
 
@@ -25,7 +29,7 @@ def _untok(t, n, c, h, w):
 @pytest.mark.parametrize("k,stride,pad,mode", [(3, 2, 1, "max"), (2, 2, 0, "max"), (8, 8, 0, "max"), (2, 2, 0, "avg")])
 def test_pool2d(k, stride, pad, mode):
     from mofa_video_amd import ops
-    x = torch.randn(2, 64, 24, 40).half().float()
+    x = torch.randn(2, 64, 24, 40, generator=_gen(11)).half().float()
     y, ho, wo = ops.pool2d(_tok(x), 2, 24, 40, 64, k, stride, pad=pad, mode=mode)
     ref = F.max_pool2d(x, k, stride, pad) if mode == "max" else F.avg_pool2d(x, k, stride)
     assert (ho, wo) == tuple(ref.shape[2:])
@@ -36,11 +40,12 @@ def test_pool2d(k, stride, pad, mode):
 def test_resize_bilinear_align_corners(hw):
     from mofa_video_amd import ops
     (h, w), (ho, wo) = hw
-    x = torch.randn(3, 128, h, w).half().float()
+    g = _gen(12)
+    x = torch.randn(3, 128, h, w, generator=g).half().float()
     y = ops.resize_bilinear_ac(_tok(x), 3, h, w, 128, ho, wo)
     ref = F.interpolate(x, size=(ho, wo), mode="bilinear", align_corners=True)
     assert torch.allclose(_untok(y, 3, 128, ho, wo), ref, atol=2e-3, rtol=2e-3)
-    f = torch.randn(2, 2, h, w)
+    f = torch.randn(2, 2, h, w, generator=g)
     assert torch.allclose(ops.resize_bilinear_ac_f32(f.to(DEV), ho, wo).cpu(),
                           F.interpolate(f, size=(ho, wo), mode="bilinear", align_corners=True), atol=1e-5, rtol=1e-5)
 
@@ -48,7 +53,7 @@ def test_resize_bilinear_align_corners(hw):
 def test_flow_expectation():
     from mofa_video_amd import ops
     from oracle.cmp import Fuser
-    logits = (torch.randn(2, 198, 12, 20) * 3).half().float()
+    logits = (torch.randn(2, 198, 12, 20, generator=_gen(13)) * 3).half().float()
     buf = torch.zeros(2 * 12 * 20, 256, dtype=torch.float16, device=DEV)
     buf[:, :198] = _tok(logits)
     got = ops.flow_expectation(buf, 2, 12, 20, 99, 50).cpu()
@@ -61,9 +66,10 @@ def test_conv_dilation_and_kernel_sizes(ksize, stride, dil):
     from mofa_video_amd import ops
     from mofa_video_amd import weights as Wt
     n, c, h, w, nout = 2, 64, 24, 40, 128
-    x = torch.randn(n, c, h, w).half().float()
-    wt = (torch.randn(nout, c, ksize, ksize) * 0.05).half().float()
-    b = torch.randn(nout)
+    gen = _gen(14)
+    x = torch.randn(n, c, h, w, generator=gen).half().float()
+    wt = (torch.randn(nout, c, ksize, ksize, generator=gen) * 0.05).half().float()
+    b = torch.randn(nout, generator=gen)
     g = ops.conv3x3_geom(h, w, stride=stride, ksize=ksize, dil=dil)
     y = ops.igemm(_tok(x), Wt.pack_conv3x3(wt).to(DEV), bias=b.to(DEV), geom=g, act=L.ACT_RELU)
     ref = F.relu(F.conv2d(x, wt, b, stride=stride, padding=dil * (ksize // 2), dilation=dil))
