@@ -156,6 +156,17 @@ int mofa_attn_temporal_f16(const void* q, const void* k, const void* v, void* ou
 int mofa_attn_temporal_masked_f16(const void* q, const void* k, const void* v, void* out,
                                   int nclips, int Tq, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
                                   float scale, uint32_t key_mask, mofa_stream_t stream);
+/* temporal self-attention over 1 <= T <= 128 frames per (clip, pixel, head), head_dim 64 or 128: the entry point for clips
+ * of more than 32 frames (it accepts shorter ones too, and then agrees with mofa_attn_temporal_f16 up to fp32 summation
+ * order).  Row layout of mofa_attn_temporal_f16 with Tq == T: q / k / v / out token row of (clip b, frame t, pixel p) =
+ * (b*T + t)*HW + p, leading dims ld (q), ldkv (k and v), ldo (out), all multiples of 8.  No key mask and no Tq < T:
+ * frame-sharded clips stay with the 32-key entry points above.  One wave per sequence keeps ceil(T/32) key tiles of K and
+ * V in LDS (read from memory once) and the score tiles of one 32-query block in registers; rows of frames >= T are never
+ * read or written.  MOFA_EINVAL for NULL pointers, T < 1 or T > 128, another head_dim, a leading dimension that is not a
+ * positive multiple of 8, or a non-positive count -- all checked before any device call. */
+int mofa_attn_temporal_long_f16(const void* q, const void* k, const void* v, void* out,
+                                int nclips, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
+                                float scale, mofa_stream_t stream);
 /* in-place row softmax of an fp16 [rows][cols] matrix (VAE mid-block attention, 1 head x 512) */
 int mofa_softmax_rows_f16(void* x, int rows, int cols, int ld, mofa_stream_t stream);
 

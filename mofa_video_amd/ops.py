@@ -427,16 +427,27 @@ def attn_spatial(q, k, v, nframes, heads, S, head_dim=64, scale=None, out=None, 
 
 def attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=None, Tq=None, key_mask=None):
     """k/v hold T frames per clip; q holds Tq <= T (Tq < T: frame-sharded clip with all-gathered K/V).  key_mask: bit j =
-    key frame j exists (padding frames of uneven shards in the gathered buffer are masked, never read)."""
+    key frame j exists (padding frames of uneven shards in the gathered buffer are masked, never read).
+    T > 32 (up to 128): plain self-attention only (Tq == T, no mask) through mofa_attn_temporal_long_f16."""
+    Tq = T if Tq is None else Tq
+    if T > 32 and (key_mask is not None or Tq != T):
+        raise ValueError(f"temporal attention over {T} key frames with a key mask or Tq < T: frame-sharded clips are limited "
+                         "to 32 key slots")
     lib = L.load()
     assert _ld(k) == _ld(v)
-    Tq = T if Tq is None else Tq
     scale = head_dim ** -0.5 if scale is None else scale
     if out is None:
         out = torch.empty((nclips * Tq * HW, heads * head_dim), dtype=F16, device=q.device)
     else:
         _written(out)
-    if key_mask is None:
+    if T > 32:
+        t0 = TIMER.start() if TIMER is not None else None
+        L.check(lib.mofa_attn_temporal_long_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, T, HW, heads, head_dim,
+                                                _ld(q), _ld(k), _ld(out), scale, L.stream_ptr()), "mofa_attn_temporal_long_f16")
+        if t0 is not None:
+            Cc = heads * head_dim
+            TIMER.stop("attn_temporal_long_kernel", t0, flops=4.0 * T * T * Cc * nclips * HW, nbytes=8.0 * nclips * T * HW * Cc)
+    elif key_mask is None:
         L.check(lib.mofa_attn_temporal_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, Tq, T, HW, heads, head_dim,
                                            _ld(q), _ld(k), _ld(out), scale, L.stream_ptr()), "mofa_attn_temporal_f16")
     else:

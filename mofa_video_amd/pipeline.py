@@ -54,7 +54,8 @@ class FlowControlNetPipelineOutput:
     controlnet_flow: Union[List, np.ndarray, torch.FloatTensor]
 
 
-MAX_TEMPORAL_FRAMES = 32        # mofa_attn_temporal_f16 holds one clip's keys in a wave: T <= 32
+MAX_TEMPORAL_FRAMES = 32        # mofa_attn_temporal_f16 holds one clip's keys in one score tile: the default limit per forward pass
+MAX_TEMPORAL_FRAMES_LONG = 128  # mofa_attn_temporal_long_f16 (four key tiles): what max_temporal_frames=... can raise it to
 GRAPH_STEPS_DEFAULT = os.environ.get("MOFA_GRAPH_STEPS", "0") == "1"
 
 
@@ -77,10 +78,17 @@ class _Shard:
 
 class FlowControlNetPipeline:
     def __init__(self, vae=None, image_encoder=None, unet=None, controlnet=None, scheduler=None,
-                 feature_extractor=None, parallel=None, round_latents_to_fp16=False):
+                 feature_extractor=None, parallel=None, round_latents_to_fp16=False, max_temporal_frames: int = MAX_TEMPORAL_FRAMES):
         """parallel: optional ``parallel.FrameParallel`` -- this process then computes one CFG half / one frame shard
         of every clip (mofa_video_amd/parallel.py); all ranks must call the pipeline with identical inputs.
-        round_latents_to_fp16: round the latents to fp16 after every Euler step, as the reference's fp16 run does."""
+        round_latents_to_fp16: round the latents to fp16 after every Euler step, as the reference's fp16 run does.
+        max_temporal_frames: the most frames one forward pass may hold (``num_frames``, or ``window_size`` of the window
+        loop), 1 .. 128.  Above the default of 32 the temporal attention runs through mofa_attn_temporal_long_f16; clips
+        sharded over ranks (``parallel``) stay limited to 32."""
+        if isinstance(max_temporal_frames, bool) or not isinstance(max_temporal_frames, int) \
+                or not 1 <= max_temporal_frames <= MAX_TEMPORAL_FRAMES_LONG:
+            raise ValueError(f"max_temporal_frames must be an integer in 1 .. {MAX_TEMPORAL_FRAMES_LONG}, got {max_temporal_frames!r}")
+        self.max_temporal_frames = max_temporal_frames
         self.vae, self.image_encoder, self.unet, self.controlnet = vae, image_encoder, unet, controlnet
         self.scheduler, self.feature_extractor = scheduler, feature_extractor
         self.vae_scale_factor = 8
@@ -118,7 +126,7 @@ class FlowControlNetPipeline:
                                             if k in EulerDiscreteScheduler().config})
         except OSError:
             sch = EulerDiscreteScheduler()
-        names = ("face_controlnet", "drag_controlnet", "parallel", "round_latents_to_fp16", "feature_extractor")
+        names = ("face_controlnet", "drag_controlnet", "parallel", "round_latents_to_fp16", "feature_extractor", "max_temporal_frames")
         kw = {k: v for k, v in modules.items() if k in names}
         if controlnet is not None:
             kw["controlnet"] = controlnet
@@ -261,9 +269,15 @@ class FlowControlNetPipeline:
                              "own forward accepts: its controlnet_condition / added_time_ids are not repeated)")
         if not max_guidance_scale > 1.0:
             raise ValueError("the reference pipeline is only well-defined with classifier-free guidance on")
-        if frames_per_forward > MAX_TEMPORAL_FRAMES:
+        limit = getattr(self, "max_temporal_frames", MAX_TEMPORAL_FRAMES)
+        if frames_per_forward > limit:
             raise ValueError(f"{frames_per_forward} frames per forward pass: the temporal attention kernel handles at most "
-                             f"{MAX_TEMPORAL_FRAMES} (use KeypointFlowControlNetPipeline's window loop for long clips)")
+                             f"{limit} (use KeypointFlowControlNetPipeline's window loop for long clips"
+                             + (f", or build the pipeline with max_temporal_frames=... up to {MAX_TEMPORAL_FRAMES_LONG})"
+                                if limit < MAX_TEMPORAL_FRAMES_LONG else ")"))
+        if frames_per_forward > MAX_TEMPORAL_FRAMES and self.parallel is not None:
+            raise ValueError(f"{frames_per_forward} frames per forward pass with parallel=...: clips sharded over ranks are limited "
+                             f"to {MAX_TEMPORAL_FRAMES} frames (their gathered keys carry a 32-bit mask); run long clips on one device")
 
     def prepare_latents(self, batch_size, num_frames, num_channels_latents, height, width, generator, latents=None):
         shape = (batch_size, num_frames, num_channels_latents // 2, height // 8, width // 8)
@@ -497,9 +511,10 @@ def _blend_residuals(df, mf, dd, md, masks, nframes):
 
 class HybridFlowControlNetPipeline(FlowControlNetPipeline):
     def __init__(self, vae=None, image_encoder=None, unet=None, face_controlnet=None, drag_controlnet=None,
-                 scheduler=None, feature_extractor=None, parallel=None, round_latents_to_fp16=False):
+                 scheduler=None, feature_extractor=None, parallel=None, round_latents_to_fp16=False,
+                 max_temporal_frames: int = MAX_TEMPORAL_FRAMES):
         super().__init__(vae, image_encoder, unet, face_controlnet, scheduler, feature_extractor, parallel=parallel,
-                         round_latents_to_fp16=round_latents_to_fp16)
+                         round_latents_to_fp16=round_latents_to_fp16, max_temporal_frames=max_temporal_frames)
         self.face_controlnet, self.drag_controlnet = face_controlnet, drag_controlnet
 
     @torch.no_grad()
@@ -577,9 +592,10 @@ class KeypointFlowControlNetPipeline(FlowControlNetPipeline):
       and the chunks not decoded early are dealt evenly after the loop."""
 
     def __init__(self, vae=None, image_encoder=None, unet=None, controlnet=None, scheduler=None, feature_extractor=None,
-                 parallel=None, round_latents_to_fp16=False, drag_controlnet=None, overlap_decode=True):
+                 parallel=None, round_latents_to_fp16=False, drag_controlnet=None, overlap_decode=True,
+                 max_temporal_frames: int = MAX_TEMPORAL_FRAMES):
         super().__init__(vae, image_encoder, unet, controlnet, scheduler, feature_extractor, parallel=parallel,
-                         round_latents_to_fp16=round_latents_to_fp16)
+                         round_latents_to_fp16=round_latents_to_fp16, max_temporal_frames=max_temporal_frames)
         self.drag_controlnet = drag_controlnet
         self.overlap_decode = overlap_decode
 
