@@ -61,6 +61,31 @@ class Ctx:
         self.halves = None        # [Ctx(1, T), Ctx(1, T)] of a B = 2 context whose CFG halves are evaluated separately (pipeline.py)
 
 
+def make_ctx(net, timestep, encoder_hidden_states, added_time_ids, B, T, base=None, half=None, par=None):
+    """The ``Ctx`` of one forward pass of ``net`` (anything with ``time``, ``temb_batch`` and ``device``: the UNet, an adapter).
+    B, T = LOCAL batch / frame counts.  half: global CFG-half index when this rank computes one half only
+    (encoder_hidden_states / added_time_ids are then still the global 2-row tensors); par: FrameParallel."""
+    c = base if base is not None else Ctx(B, T)
+    ts = torch.as_tensor(timestep, dtype=torch.float32, device=net.device).reshape(-1)
+    ts = ts.expand(B).contiguous() if ts.numel() == 1 else ts.contiguous()
+    ids = added_time_ids.to(net.device, torch.float32)
+    if half is not None:
+        ids = ids[half:half + B]
+    c.temb_act = net.time(ts, ids.contiguous())
+    c.temb_all = net.temb_batch.run(c.temb_act)
+    if c.ctx16 is None:
+        e = encoder_hidden_states.to(net.device, torch.float32)
+        e = e.reshape(e.shape[0], -1).contiguous()
+        if half is not None:
+            c.ctx16_all = ops.cast_f32_to_f16(e)
+            c.ctx16 = c.ctx16_all[half:half + B].contiguous()
+            c.half = half
+        else:
+            c.ctx16 = ops.cast_f32_to_f16(e)
+    c.par = par
+    return c
+
+
 # ---------------------------------------------------------------------------------------------------------
 class Linear:
     def __init__(self, s, pad_n=False):

@@ -5,15 +5,18 @@
 Same constructor modules, ``__call__`` signatures, defaults (``output_type="pil"``) and return types.  The denoise loops run
 entirely in libmofa_hip.so on token-major fp16 activations:
 
-    per clip (hoisted, timestep-invariant -- SURVEY F7/F11):
+    per call (``_prologue``): checks, image conditioning, schedule, initial latents, the adapter's condition image
+    per clip (``_run_clip``; hoisted, timestep-invariant -- SURVEY F7/F11):
         adapter.prepare_condition  (cond CNN, first-frame pyramid, flow pyramids, 96 forward-splat warps)
-        cross-attention row vectors and frame-position embeddings of every transformer layer
-    per step:
-        mofa_prepare_model_input   (scale by 1/sqrt(sigma^2+1), concat image latents, both CFG halves)
-        FlowControlNet.forward_tokens -> 12 + 1 residuals   (Hybrid: two adapters + mask blend)
-        UNet.forward_tokens           -> noise prediction
-        mofa_cfg_euler_step         (CFG with per-frame guidance + v-prediction Euler step, fp32 latents)
-    decode: temporal VAE decoder, chunks of ``decode_chunk_size`` frames.
+        cross-attention row vectors and frame-position embeddings of every transformer layer (cached in the ``Ctx``s)
+        scheduler.step_table       (sigma, sigma_next, timestep, 1 / sqrt(sigma^2 + 1) of every step: ONE upload, ``_clip_loop``)
+    per step (``_Step``; with ``graph_steps`` the steps 1 .. n-1 are replays of ONE captured hipGraph, ``_clip_loop``):
+        mofa_prepare_model_input_dev  (scale by 1/sqrt(sigma^2+1), concat image latents, both CFG halves; scalars: the table row)
+        adapter trunk(s) -> 12 + 1 residuals (Hybrid: two adapters + mask blend) || UNet encoder; UNet decoder  (``_denoise_forward``)
+        mofa_cfg_euler_step_dev       (CFG with per-frame guidance + v-prediction Euler step, fp32 latents, in place)
+    decode (``_decode``): temporal VAE decoder, chunks of ``decode_chunk_size`` frames.
+The Keypoint window loop (``_WindowLoop``) runs the same step body per window with the scheduler's numbers as host scalars
+(mofa_prepare_model_input / mofa_cfg_euler_step) and averages the overlapping windows as ``WindowPlan`` says.
 
 Within a step the adapter's ControlNet trunk(s) and the UNet's encoder half (conv_in, down blocks, mid block) do not depend
 on each other (the residuals are added after the mid block): without frame sharding the trunks are enqueued on a second HIP
@@ -35,6 +38,9 @@ Reference quirks kept: ``added_time_ids`` is always [6, 128, 0.02] (pipeline.py:
 seed does not reproduce the reference's fp16 CUDA draws -- pass ``latents=`` for reproducibility across implementations;
 (3) the scheduler's unused per-step randn draw is not made (no effect on results).
 """
+import collections
+import contextlib
+import functools
 import os
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Union
@@ -43,7 +49,7 @@ import numpy as np
 import torch
 
 from . import frontend, ops
-from .blocks import Ctx
+from .blocks import Ctx, drive, run_lockstep
 from .output import tensor2vid
 from .vae import decode_latents
 
@@ -63,7 +69,7 @@ class _Shard:
     """what this rank computes of a T-frame clip (mofa_video_amd/parallel.py): frames [f0, f1), Bl CFG halves"""
 
     def __init__(self, par, T):
-        self.par = par
+        self.par, self.T = par, T
         self.lay = par.lay if par is not None else None
         if self.lay is not None and self.lay.T != T:
             raise ValueError(f"the parallel Layout was built for {self.lay.T} frames, the clip has {T}")
@@ -74,6 +80,60 @@ class _Shard:
         self.fpar = par if (self.lay is not None and self.lay.sharded_frames) else None
         self.world = self.lay.world if self.lay is not None else 1
         self.rank = self.lay.rank if self.lay is not None else 0
+
+    def guidance(self, gmin, gmax):
+        """the guidance scales of this shard's first and last frame: per-frame guidance is linear in the frame of the clip"""
+        gspan = (gmax - gmin) / max(self.T - 1, 1)
+        return gmin + gspan * self.f0, gmin + gspan * (self.f1 - 1)
+
+    def gather(self, lat, h, w):
+        """this shard's stepped latents [Tl,4,h,w] -> the clip's [T,4,h,w] on every rank"""
+        if self.fpar is None:
+            return lat
+        return self.fpar.gather_frames(lat.reshape(self.Tl, 4 * h * w), 1).reshape(self.T, 4, h, w)
+
+
+def _rows_of(tt, hf):                                                  # CFG half ``hf`` of a token tensor that holds both
+    n = tt.shape[0] // 2
+    return tt[hf * n:(hf + 1) * n]
+
+
+class _Step:
+    """THE denoise step of every loop: model input -> adapter trunk(s) + UNet -> CFG + Euler step, on this rank's CFG half /
+    frames ``sh`` of a clip or window.  Holds the model-input buffer and what no step changes; ``adapters`` / ``c_un`` (the
+    networks' per-clip caches) are arguments because the window loop keeps one set per window.  ``scal`` says where the
+    scheduler's numbers come from: a row of the device step table (the ``_dev`` entry points read it on the device, which makes
+    a step capturable) or the host scalars (timestep, sigma, sigma_next).  The two forms differ by up to 1 fp16 ulp in the
+    model input (tests/test_kernels_gpu.py::test_device_scalar_scheduler_kernels), so a loop stays with the form it has."""
+
+    def __init__(self, pipe, sh, il, emb, networks, masks, h, w, g0, g1, round16=False):
+        self.pipe, self.sh, self.il, self.emb, self.masks, self.h, self.w, self.g0, self.g1 = pipe, sh, il, emb, masks, h, w, g0, g1
+        self.round16 = round16
+        self.added_time_ids = torch.tensor([[6.0, 128.0, 0.02]] * 2, dtype=torch.float32, device=pipe.device)   # :430-440
+        rows = sh.Tl * h * w
+        in_ld = max(net.in_ld for net in [pipe.unet] + list(networks))
+        self.x_in = torch.zeros((2 * rows, in_ld), dtype=torch.float16, device=pipe.device)
+        self.x_loc = self.x_in if sh.Bl == 2 else self.x_in[sh.half * rows:(sh.half + 1) * rows]
+
+    def __call__(self, lat, scal, adapters, c_un):
+        """steps ``lat`` fp32 [Tl,4,h,w] in place"""
+        sh, table = self.sh, torch.is_tensor(scal)
+        if table:
+            ops.prepare_model_input_dev(lat, self.il, self.x_in, scal)
+            t = scal[2:2 + sh.Bl]
+        else:
+            t, sigma, sigma_next = scal
+            ops.prepare_model_input(lat, self.il, self.x_in, sigma)
+        noise = self.pipe._denoise_forward(self.x_loc, t, self.emb, self.added_time_ids, sh.Bl, sh.Tl, sh.half, sh.fpar, self.h, self.w,
+                                           adapters, c_un, self.masks)
+        if sh.Bl == 1:
+            noise = sh.par.gather_cfg(noise)                          # both halves of this frame shard
+        if table:
+            ops.cfg_euler_step_dev_(lat, noise, scal, self.g0, self.g1)
+        else:
+            ops.cfg_euler_step_(lat, noise, sigma, sigma_next, self.g0, self.g1)
+        if self.round16:
+            ops.cast_f16_to_f32(ops.cast_f32_to_f16(lat), out=lat)
 
 
 class FlowControlNetPipeline:
@@ -133,43 +193,71 @@ class FlowControlNetPipeline:
         return cls(vae=vae, image_encoder=enc, unet=unet, scheduler=sch, **kw)
 
     # ---- one network evaluation of a denoise step ---------------------------------------------------------------------------
+    def _trunk_layers(self, adapters, masks, x_loc, t, emb, added_time_ids, Bl, Tl, half, fpar, h, w):
+        """every adapter's ControlNet trunk, one after the other, then the blend of their residuals: a layer generator
+        (``drive`` runs it through; blocks.run_lockstep interleaves it with the UNet's encoder) -> (12 residuals, mid residual)"""
+        res = []
+        for net, ctx, cond, scale in adapters:
+            net.make_ctx(t, emb, added_time_ids, Bl, Tl, base=ctx, half=half, par=fpar)
+            res.append((yield from net.forward_layers(x_loc, ctx, h, w, cond, scale)))
+        down, mid = res[0]
+        if len(res) == 2:
+            down, mid = _blend_residuals(down, mid, res[1][0], res[1][1], masks, Bl * Tl)
+        return down, mid
+
+    def _encoder_layers(self, x_loc, t, emb, added_time_ids, Bl, Tl, half, fpar, h, w, c_un):
+        self.unet.make_ctx(t, emb, added_time_ids, Bl, Tl, base=c_un, half=half, par=fpar)
+        return (yield from self.unet.encode_layers(x_loc, c_un, h, w))
+
     def _denoise_forward(self, x_loc, t, emb, added_time_ids, Bl, Tl, half, fpar, h, w, adapters, c_un, masks=None):
         """``adapters``: [(controlnet, its Ctx, its per-clip condition, conditioning scale)], one entry, or two (face, drag)
         whose residuals are blended by ``masks`` (Hybrid/pipeline/pipeline.py:479-489) -> the UNet's noise prediction (tokens).
         Without frame sharding the trunks run on ``self._adapter_stream`` while the UNet's encoder half runs on the caller's
         stream; the streams join before the residuals are added (unet.decode_tokens).  Frame-sharded ranks enqueue the two
-        networks layer by layer in lockstep so that their exchanges are issued in program order (_denoise_forward_sharded)."""
+        networks layer by layer in lockstep so that their exchanges are issued in program order."""
         unet = self.unet
-
-        def trunks():
-            res = []
-            for net, ctx, cond, scale in adapters:
-                net.make_ctx(t, emb, added_time_ids, Bl, Tl, base=ctx, half=half, par=fpar)
-                res.append(net.forward_tokens(x_loc, ctx, h, w, cond, scale))
-            down, mid = res[0]
-            if len(res) == 2:
-                down, mid = _blend_residuals(down, mid, res[1][0], res[1][1], masks, Bl * Tl)
-            return down, mid
-
+        net_args = (x_loc, t, emb, added_time_ids, Bl, Tl, half, fpar, h, w)
+        trunks = self._trunk_layers(adapters, masks, *net_args)
         if not self.overlap_adapter or (fpar is not None and not fpar.two_streams):
-            down, mid = trunks()
+            down, mid = drive(trunks)
             unet.make_ctx(t, emb, added_time_ids, Bl, Tl, base=c_un, half=half, par=fpar)
             return unet.forward_tokens(x_loc, c_un, h, w, down, mid)
-        if fpar is not None:
-            return self._denoise_forward_sharded(adapters, masks, x_loc, t, emb, added_time_ids, Bl, Tl, half, fpar, h, w, c_un)
         cur = torch.cuda.current_stream(self.device)
         if self._adapter_stream is None:
             self._adapter_stream = torch.cuda.Stream(device=self.device)
         side = self._adapter_stream
         side.wait_stream(cur)                                   # the model input (and everything before it) is ready
-        with torch.cuda.stream(side):
-            down, mid = trunks()
-        unet.make_ctx(t, emb, added_time_ids, Bl, Tl, base=c_un, half=half, par=fpar)
-        enc = unet.encode_tokens(x_loc, c_un, h, w)
+        if fpar is None:
+            with torch.cuda.stream(side):
+                down, mid = drive(trunks)
+            unet.make_ctx(t, emb, added_time_ids, Bl, Tl, base=c_un, half=half, par=fpar)
+            enc = unet.encode_tokens(x_loc, c_un, h, w)
+        else:
+            # Frame-sharded ranks: trunk(s) and UNet encoder still overlap on two HIP streams, but both issue collectives, and all
+            # ranks must issue them in one order.  ONE host thread therefore enqueues both networks layer by layer in lockstep
+            # (blocks.run_lockstep: a trunk layer on the second stream, the matching encoder layer on the caller's, ...): the order
+            # is the program order on every rank, each network's wait for its GroupNorm partials / halo frames / token gather is a
+            # stream wait covered by the other network's kernels, and the host never blocks (a second host thread under a turn
+            # token gave the same order at 2.3 x the host time per step, profiles/r04_shard_proxy.log).  The decoder half runs on
+            # the caller's stream alone.
+            @contextlib.contextmanager
+            def on_side():
+                fpar.lane = 0
+                with torch.cuda.stream(side):
+                    yield
+
+            @contextlib.contextmanager
+            def on_cur():
+                fpar.lane = 1
+                yield
+            try:
+                (down, mid), enc = run_lockstep([trunks, self._encoder_layers(*net_args, c_un)], [on_side, on_cur])
+            finally:
+                fpar.lane = 0
         cur.wait_stream(side)
         for r in list(down) + [mid]:                            # allocated on the side stream, consumed (and freed) on this one
             r.record_stream(cur)
-        if not (self.split_decoder and Bl == 2 and half is None):
+        if fpar is not None or not (self.split_decoder and Bl == 2 and half is None):
             return unet.decode_tokens(enc, c_un, down, mid)
         # The UNet's decoder half has nothing to run beside, so its two CFG halves go down the two streams (rows [0, rows) and
         # [rows, 2 rows) of every token tensor; the per-half contexts are the ones a rank of the 2-way CFG layout uses): one
@@ -189,65 +277,11 @@ class FlowControlNetPipeline:
             with torch.cuda.stream(st):
                 ch = c_un.halves[hf]
                 unet.make_ctx(t[hf:hf + 1] if torch.is_tensor(t) else t, emb, added_time_ids, 1, Tl, base=ch, half=hf, par=None)
-
-                def rows_of(tt, hf=hf):
-                    n = tt.shape[0] // 2
-                    return tt[hf * n:(hf + 1) * n]
-                outs[hf] = unet.decode_tokens((rows_of(sample), [rows_of(k) for k in skips], counts, Hm, Wm), ch,
-                                              [rows_of(r) for r in down], rows_of(mid))
+                outs[hf] = unet.decode_tokens((_rows_of(sample, hf), [_rows_of(k, hf) for k in skips], counts, Hm, Wm), ch,
+                                              [_rows_of(r, hf) for r in down], _rows_of(mid, hf))
         cur.wait_stream(side)
         outs[1].record_stream(cur)
         return torch.cat(outs, 0)
-
-    def _denoise_forward_sharded(self, adapters, masks, x_loc, t, emb, added_time_ids, Bl, Tl, half, fpar, h, w, c_un):
-        """Frame-sharded ranks: trunk(s) and UNet encoder still overlap on two HIP streams, but both issue collectives, and all
-        ranks must issue them in one order.  ONE host thread therefore enqueues both networks layer by layer in lockstep
-        (blocks.run_lockstep: a trunk layer on the second stream, the matching encoder layer on the caller's, ...): the order
-        is the program order on every rank, each network's wait for its GroupNorm partials / halo frames / token gather is a
-        stream wait covered by the other network's kernels, and the host never blocks (a second host thread under a turn
-        token gave the same order at 2.3 x the host time per step, profiles/r04_shard_proxy.log).  The decoder half runs on the
-        caller's stream alone."""
-        import contextlib
-        from .blocks import run_lockstep
-        unet, dev = self.unet, self.device
-        cur = torch.cuda.current_stream(dev)
-        if self._adapter_stream is None:
-            self._adapter_stream = torch.cuda.Stream(device=dev)
-        side = self._adapter_stream
-        side.wait_stream(cur)
-
-        def trunk_layers():
-            res = []
-            for net, ctx, cond, scale in adapters:
-                net.make_ctx(t, emb, added_time_ids, Bl, Tl, base=ctx, half=half, par=fpar)
-                res.append((yield from net.forward_layers(x_loc, ctx, h, w, cond, scale)))
-            down, mid = res[0]
-            if len(res) == 2:
-                down, mid = _blend_residuals(down, mid, res[1][0], res[1][1], masks, Bl * Tl)
-            return down, mid
-
-        def encoder_layers():
-            unet.make_ctx(t, emb, added_time_ids, Bl, Tl, base=c_un, half=half, par=fpar)
-            return (yield from unet.encode_layers(x_loc, c_un, h, w))
-
-        @contextlib.contextmanager
-        def on_side():
-            fpar.lane = 0
-            with torch.cuda.stream(side):
-                yield
-
-        @contextlib.contextmanager
-        def on_cur():
-            fpar.lane = 1
-            yield
-        try:
-            (down, mid), enc = run_lockstep([trunk_layers(), encoder_layers()], [on_side, on_cur])
-        finally:
-            fpar.lane = 0
-        cur.wait_stream(side)
-        for r in list(down) + [mid]:
-            r.record_stream(cur)
-        return unet.decode_tokens(enc, c_un, down, mid)
 
     # ---- pieces of the reference __call__ ---------------------------------------------------------------------------------
     def check_inputs(self, image, height, width):                      # pipeline.py:222-234
@@ -269,7 +303,7 @@ class FlowControlNetPipeline:
                              "own forward accepts: its controlnet_condition / added_time_ids are not repeated)")
         if not max_guidance_scale > 1.0:
             raise ValueError("the reference pipeline is only well-defined with classifier-free guidance on")
-        limit = getattr(self, "max_temporal_frames", MAX_TEMPORAL_FRAMES)
+        limit = self.max_temporal_frames
         if frames_per_forward > limit:
             raise ValueError(f"{frames_per_forward} frames per forward pass: the temporal attention kernel handles at most "
                              f"{limit} (use KeypointFlowControlNetPipeline's window loop for long clips"
@@ -329,7 +363,8 @@ class FlowControlNetPipeline:
             return lat
         return ops.cast_f16_to_f32(ops.cast_f32_to_f16(lat.contiguous())).reshape(lat.shape)
 
-    def _clip_loop(self, lat, il, emb, added_time_ids, adapters, c_un, masks, sh, h, w, g0, g1, callback):
+
+    def _clip_loop(self, lat, step, adapters, c_un, callback):
         """The denoise loop of one clip (pipeline.py:447-511) on this rank's CFG half / frames: ``lat`` fp32 [Tl,4,h,w] is stepped
         in place through every timestep of the scheduler and returned.
 
@@ -339,31 +374,15 @@ class FlowControlNetPipeline:
         kernel set-up, per-clip caches), the second is captured in a hipGraph on the loop's own stream -- its first node copies
         row ``counter`` of the table into a fixed ``cur`` row and increments the counter, every other node reads ``cur`` -- and
         steps 1 .. n-1 are replays: the host issues one graph launch per step instead of ~1 400 kernel launches."""
-        sch, dev, unet = self.scheduler, self.device, self.unet
-        Tl, Bl, half, fpar = sh.Tl, sh.Bl, sh.half, sh.fpar
-        rows = Tl * h * w
-        in_ld = max([unet.in_ld] + [a[0].in_ld for a in adapters])
-        x_in = torch.zeros((2 * rows, in_ld), dtype=torch.float16, device=dev)
-        x_loc = x_in if Bl == 2 else x_in[half * rows:(half + 1) * rows]
-        timesteps = sch.timesteps
-        n = len(timesteps)
+        sch, dev, sh = self.scheduler, self.device, step.sh
+        n = len(sch.timesteps)
         self._num_timesteps = n
         tab = torch.from_numpy(sch.step_table()).to(dev)
-
-        def step(scal):
-            ops.prepare_model_input_dev(lat, il, x_in, scal)
-            noise = self._denoise_forward(x_loc, scal[2:2 + Bl], emb, added_time_ids, Bl, Tl, half, fpar, h, w, adapters, c_un, masks)
-            if Bl == 1:
-                noise = sh.par.gather_cfg(noise)                          # both halves of this frame shard
-            ops.cfg_euler_step_dev_(lat, noise, scal, g0, g1)
-            if self.round_latents_to_fp16:
-                ops.cast_f16_to_f32(ops.cast_f32_to_f16(lat), out=lat)
-
         if not (self.graph_steps and callback is None and sh.par is None and ops.TIMER is None and n >= 3):
-            for i, t in enumerate(timesteps):
-                step(tab[i])
+            for i, t in enumerate(sch.timesteps):
+                step(lat, tab[i], adapters, c_un)
                 if callback is not None:
-                    new = self._callback(callback, i, t, lat, (1, Tl, 4, h, w))
+                    new = self._callback(callback, i, t, lat, (1, sh.Tl, 4, step.h, step.w))
                     if new is not lat:
                         lat.copy_(new)
             return lat
@@ -374,16 +393,14 @@ class FlowControlNetPipeline:
         gs.wait_stream(caller)
         counter = torch.zeros(1, dtype=torch.int32, device=dev)
         cur = torch.empty(ops.STEP_SCALARS, dtype=torch.float32, device=dev)
-
-        def body():
-            ops.step_select(tab, counter, cur)
-            step(cur)
         with torch.cuda.stream(gs):
-            body()                                                        # step 0, eager
+            ops.step_select(tab, counter, cur)
+            step(lat, cur, adapters, c_un)                                # step 0, eager
             graph = torch.cuda.CUDAGraph()
             graph.capture_begin()
             try:
-                body()                                                    # (recorded, not executed)
+                ops.step_select(tab, counter, cur)
+                step(lat, cur, adapters, c_un)                            # (recorded, not executed)
             finally:
                 graph.capture_end()
             for _ in range(1, n):
@@ -402,36 +419,72 @@ class FlowControlNetPipeline:
             lat = out["latents"].to(self.device, torch.float32).reshape(lat.shape).contiguous()
         return lat
 
-    def _decode(self, latents_out, T, decode_chunk_size, output_type, sh, stream_chunks=None):
+    def _decode(self, latents, T, decode_chunk_size, output_type, world, rank, owner=None, stream_chunks=None):
         """decode_latents + tensor2vid (pipeline.py:513-518).  With several ranks the independent VAE chunks (:204-213) are
-        dealt round-robin (or as ``sh.owner`` says): the result is then the list of (first_frame, frames) chunks this rank
-        decoded.  stream_chunks: {chunk index: raw fp32 [n,3,H,W]} already decoded on a side stream (Keypoint loop)."""
+        dealt round-robin (or as ``owner`` says: {chunk index: rank}): the result is then the list of (first_frame, frames)
+        chunks this rank decoded.  stream_chunks: {chunk index: raw fp32 [n,3,H,W]} already decoded on a side stream (Keypoint
+        loop)."""
         if output_type == "latent":
-            return latents_out
-        if sh.world == 1:
-            if stream_chunks:
-                parts = []
-                for ci, s0 in enumerate(range(0, T, decode_chunk_size)):
-                    z = latents_out[0, s0:s0 + decode_chunk_size]
-                    parts.append(stream_chunks[ci] if ci in stream_chunks else
-                                 self.vae.decode(z, num_frames=z.shape[0], _prescale=1.0 / self.vae.config.scaling_factor))
-                fr = torch.cat(parts, 0)
-                frames = fr.reshape(-1, T, *fr.shape[1:]).permute(0, 2, 1, 3, 4).float()
-            else:
-                frames = decode_latents(self.vae, latents_out, T, decode_chunk_size)   # fp32 [1,3,T,H,W]
+            return latents
+        if world == 1 and not stream_chunks:
+            frames = decode_latents(self.vae, latents, T, decode_chunk_size)           # fp32 [1,3,T,H,W]
             return frames if output_type == "raw" else tensor2vid(frames, None, output_type=output_type)
-        frames = []
+        stream_chunks = stream_chunks or {}
         sf = 1.0 / self.vae.config.scaling_factor
-        owner = getattr(sh, "owner", None)                  # Keypoint loop: chunks decoded early belong to a stated rank
+        chunks = []
         for ci, s0 in enumerate(range(0, T, decode_chunk_size)):
-            if (owner[ci] if owner else ci % sh.world) == sh.rank:
-                z = latents_out[0, s0:s0 + decode_chunk_size]
-                fr = stream_chunks[ci] if (stream_chunks and ci in stream_chunks) else \
-                    self.vae.decode(z, num_frames=z.shape[0], _prescale=sf)            # fp32 [n,3,H,W]
-                if output_type != "raw":
-                    fr = tensor2vid(fr.permute(1, 0, 2, 3).unsqueeze(0), None, output_type=output_type)[0]
-                frames.append((s0, fr))
-        return frames
+            if (owner[ci] if owner else ci % world) != rank:
+                continue
+            z = latents[0, s0:s0 + decode_chunk_size]
+            fr = stream_chunks[ci] if ci in stream_chunks else self.vae.decode(z, num_frames=z.shape[0], _prescale=sf)   # fp32 [n,3,H,W]
+            if world > 1 and output_type != "raw":
+                fr = tensor2vid(fr.permute(1, 0, 2, 3).unsqueeze(0), None, output_type=output_type)[0]
+            chunks.append((s0, fr))
+        if world > 1:
+            return chunks
+        fr = torch.cat([fr for _, fr in chunks], 0)
+        frames = fr.reshape(-1, T, *fr.shape[1:]).permute(0, 2, 1, 3, 4).float()
+        return frames if output_type == "raw" else tensor2vid(frames, None, output_type=output_type)
+
+    # ---- what the three __call__s share -------------------------------------------------------------------------------------
+    def _prologue(self, image, height, width, num_frames, frames_per_forward, decode_chunk_size, batch_size, num_videos_per_prompt,
+                  max_guidance_scale, num_inference_steps, noise_aug_strength, generator, latents, image_embeddings, image_latents,
+                  controlnet_condition, more_checks=None):
+        """Steps 1 .. 5 of the reference ``__call__`` in its order (pipeline.py:313-397): defaults, input checks (``more_checks``:
+        the calling class's own, after the common ones), image conditioning (computed before the hot path), schedule, initial
+        latents (every rank prepares the full clip's and keeps its own frames later) and the adapter's condition image (identical
+        for both CFG halves, :393-397 -> computed once) -> (T, decode_chunk_size, h, w, emb, il, lat fp32 [T,4,h,w], cond)"""
+        T = num_frames if num_frames is not None else self.unet.config.num_frames
+        decode_chunk_size = decode_chunk_size if decode_chunk_size is not None else T
+        self.check_inputs(image, height, width)
+        self._check_call(batch_size, num_videos_per_prompt, max_guidance_scale, frames_per_forward if frames_per_forward is not None else T)
+        if more_checks is not None:
+            more_checks(T)
+        h, w = height // 8, width // 8
+        emb, il = self._conditioning(image, image_embeddings, image_latents, height, width, noise_aug_strength, generator)
+        self.scheduler.set_timesteps(num_inference_steps)
+        lat = self.prepare_latents(1, T, self.unet.config.in_channels, height, width, generator, latents).reshape(T, 4, h, w).contiguous()
+        cond = self._condition_image(controlnet_condition, height, width)
+        return T, decode_chunk_size, h, w, emb, il, lat, cond
+
+    def _run_clip(self, sh, lat, il, emb, networks, masks, h, w, gmin, gmax, callback):
+        """Denoise one clip on this rank's shard ``sh`` of it (2-way CFG x frame shards) and reassemble the
+        clip's latents on every rank.  lat: the whole clip's fp32 [T,4,h,w]; networks: [(adapter, its ``prepare_condition`` for
+        the frames (sh.f0, sh.f1), its conditioning scale)], two of them with the ``masks`` that blend their residuals."""
+        lat = lat[sh.f0:sh.f1].contiguous()
+        g0, g1 = sh.guidance(gmin, gmax)
+        step = _Step(self, sh, il, emb, [net for net, _, _ in networks], masks, h, w, g0, g1, self.round_latents_to_fp16)
+        adapters = [(net, Ctx(sh.Bl, sh.Tl), cond, scale) for net, cond, scale in networks]   # the Ctxs hold the per-clip caches
+        lat = self._clip_loop(lat, step, adapters, Ctx(sh.Bl, sh.Tl), callback)                # :447-511
+        return sh.gather(lat, h, w)
+
+    def _epilogue(self, lat, decode_chunk_size, output_type, return_dict, controlnet_flow, world, rank, owner=None, stream_chunks=None):
+        """lat: the clip's final latents [T,4,h,w] -> what ``__call__`` returns (pipeline.py:513-527)"""
+        T = lat.shape[0]
+        frames = self._decode(lat.reshape(1, T, *lat.shape[1:]), T, decode_chunk_size, output_type, world, rank, owner, stream_chunks)
+        if not return_dict:
+            return frames, controlnet_flow
+        return FlowControlNetPipelineOutput(frames=frames, controlnet_flow=controlnet_flow)
 
     # ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -444,45 +497,15 @@ class FlowControlNetPipeline:
                  callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], return_dict: bool = True,
                  controlnet_cond_scale=1.0, batch_size=1, *, image_embeddings=None, image_latents=None):
-        unet, cn, sch, dev = self.unet, self.controlnet, self.scheduler, self.device
-        num_frames = num_frames if num_frames is not None else unet.config.num_frames
-        decode_chunk_size = decode_chunk_size if decode_chunk_size is not None else num_frames
-        self.check_inputs(image, height, width)
-        self._check_call(batch_size, num_videos_per_prompt, max_guidance_scale, num_frames)
-        h, w = height // 8, width // 8
-        T = num_frames
-
-        # 3./4. image conditioning (computed before the hot path)
-        emb, il = self._conditioning(image, image_embeddings, image_latents, height, width, noise_aug_strength, generator)
-
-        # 4./5. schedule + latents (every rank prepares the full clip's latents; it keeps its own frames below)
-        sch.set_timesteps(num_inference_steps)
-        timesteps = sch.timesteps
-        lat = self.prepare_latents(1, T, unet.config.in_channels, height, width, generator, latents)
-        lat = lat.reshape(T, 4, h, w).contiguous()
-
-        # adapter condition: identical for both CFG halves (:393-397) -> computed once
-        cond = self._condition_image(controlnet_condition, height, width)
-        flow = controlnet_flow.to(dev, torch.float32)
-        added_time_ids = torch.tensor([[6.0, 128.0, 0.02]] * 2, dtype=torch.float32, device=dev)   # :430-440
-
+        T, decode_chunk_size, h, w, emb, il, lat, cond = self._prologue(
+            image, height, width, num_frames, None, decode_chunk_size, batch_size, num_videos_per_prompt, max_guidance_scale,
+            num_inference_steps, noise_aug_strength, generator, latents, image_embeddings, image_latents, controlnet_condition)
+        flow = controlnet_flow.to(self.device, torch.float32)
         sh = _Shard(self.parallel, T)
-        f0, f1, Tl, Bl, half, fpar = sh.f0, sh.f1, sh.Tl, sh.Bl, sh.half, sh.fpar
-        warped = cn.prepare_condition(cond[:1], flow[:1], frames=(f0, f1))
-        lat = lat[f0:f1].contiguous()
-        gspan = (max_guidance_scale - min_guidance_scale) / max(T - 1, 1)  # per-frame guidance is linear in the frame
-        g0, g1 = min_guidance_scale + gspan * f0, min_guidance_scale + gspan * (f1 - 1)
-
-        c_cn, c_un = Ctx(Bl, Tl), Ctx(Bl, Tl)                             # hold the per-clip invariant caches
-        lat = self._clip_loop(lat, il, emb, added_time_ids, [(cn, c_cn, warped, controlnet_cond_scale)], c_un, None, sh, h, w,
-                              g0, g1, callback_on_step_end)                # :447-511
-
-        if fpar is not None:                                              # reassemble the clip's latents on every rank
-            lat = fpar.gather_frames(lat.reshape(Tl, 4 * h * w), 1).reshape(T, 4, h, w)
-        frames = self._decode(lat.reshape(1, T, 4, h, w), T, decode_chunk_size, output_type, sh)
-        if not return_dict:
-            return frames, controlnet_flow
-        return FlowControlNetPipelineOutput(frames=frames, controlnet_flow=controlnet_flow)
+        warped = self.controlnet.prepare_condition(cond[:1], flow[:1], frames=(sh.f0, sh.f1))
+        lat = self._run_clip(sh, lat, il, emb, [(self.controlnet, warped, controlnet_cond_scale)], None, h, w,
+                             min_guidance_scale, max_guidance_scale, callback_on_step_end)
+        return self._epilogue(lat, decode_chunk_size, output_type, return_dict, controlnet_flow, sh.world, sh.rank)
 
 
 # =========================================================================================================
@@ -509,6 +532,7 @@ def _blend_residuals(df, mf, dd, md, masks, nframes):
     return down, ops.mask_blend(mf, md, masks[hw], hw)
 
 
+
 class HybridFlowControlNetPipeline(FlowControlNetPipeline):
     def __init__(self, vae=None, image_encoder=None, unet=None, face_controlnet=None, drag_controlnet=None,
                  scheduler=None, feature_extractor=None, parallel=None, round_latents_to_fp16=False,
@@ -527,36 +551,18 @@ class HybridFlowControlNetPipeline(FlowControlNetPipeline):
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs: List[str] = ["latents"],
                  return_dict: bool = True, ctrl_scale_traj=1.0, ctrl_scale_ldmk=1.0, batch_size=1, *,
                  image_embeddings=None, image_latents=None):
-        unet, face, drag, sch, dev = self.unet, self.face_controlnet, self.drag_controlnet, self.scheduler, self.device
-        T = num_frames if num_frames is not None else unet.config.num_frames
-        decode_chunk_size = decode_chunk_size if decode_chunk_size is not None else T
-        self.check_inputs(image, height, width)
-        self._check_call(batch_size, num_videos_per_prompt, max_guidance_scale, T)
-        h, w = height // 8, width // 8
-        emb, il = self._conditioning(image, image_embeddings, image_latents, height, width, noise_aug_strength, generator)
-        sch.set_timesteps(num_inference_steps)
-        timesteps = sch.timesteps
-        lat = self.prepare_latents(1, T, unet.config.in_channels, height, width, generator, latents).reshape(T, 4, h, w).contiguous()
-        cond = self._condition_image(controlnet_condition, height, width)
-        # frame sharding exactly as in FlowControlNetPipeline.__call__ (2-way CFG x frame shards)
+        face, drag, dev = self.face_controlnet, self.drag_controlnet, self.device
+        T, decode_chunk_size, h, w, emb, il, lat, cond = self._prologue(
+            image, height, width, num_frames, None, decode_chunk_size, batch_size, num_videos_per_prompt, max_guidance_scale,
+            num_inference_steps, noise_aug_strength, generator, latents, image_embeddings, image_latents, controlnet_condition)
         sh = _Shard(self.parallel, T)
-        f0, f1, Tl, Bl, half, fpar = sh.f0, sh.f1, sh.Tl, sh.Bl, sh.half, sh.fpar
-        cf = face.prepare_condition(cond[:1], controlnet_flow.to(dev, torch.float32)[:1], landmarks[:1], frames=(f0, f1))
-        cd = drag.prepare_condition(cond[:1], drag_flow.to(dev, torch.float32)[:1], frames=(f0, f1))
-        lat = lat[f0:f1].contiguous()
-        gspan = (max_guidance_scale - min_guidance_scale) / max(T - 1, 1)
-        g0, g1 = min_guidance_scale + gspan * f0, min_guidance_scale + gspan * (f1 - 1)
+        fr = (sh.f0, sh.f1)
+        cf = face.prepare_condition(cond[:1], controlnet_flow.to(dev, torch.float32)[:1], landmarks[:1], frames=fr)
+        cd = drag.prepare_condition(cond[:1], drag_flow.to(dev, torch.float32)[:1], frames=fr)
         masks = _resized_masks(mask, height, width, h, w, dev)
-        added_time_ids = torch.tensor([[6.0, 128.0, 0.02]] * 2, dtype=torch.float32, device=dev)
-        c_f, c_d, c_u = Ctx(Bl, Tl), Ctx(Bl, Tl), Ctx(Bl, Tl)
-        lat = self._clip_loop(lat, il, emb, added_time_ids, [(face, c_f, cf, ctrl_scale_ldmk), (drag, c_d, cd, ctrl_scale_traj)],
-                              c_u, masks, sh, h, w, g0, g1, callback_on_step_end)
-        if fpar is not None:
-            lat = fpar.gather_frames(lat.reshape(Tl, 4 * h * w), 1).reshape(T, 4, h, w)
-        frames = self._decode(lat.reshape(1, T, 4, h, w), T, decode_chunk_size, output_type, sh)
-        if not return_dict:
-            return frames, controlnet_flow
-        return FlowControlNetPipelineOutput(frames=frames, controlnet_flow=controlnet_flow)
+        lat = self._run_clip(sh, lat, il, emb, [(face, cf, ctrl_scale_ldmk), (drag, cd, ctrl_scale_traj)], masks, h, w,
+                             min_guidance_scale, max_guidance_scale, callback_on_step_end)
+        return self._epilogue(lat, decode_chunk_size, output_type, return_dict, controlnet_flow, sh.world, sh.rank)
 
 
 # =========================================================================================================
@@ -580,6 +586,175 @@ def window_views(num_frames, window_size, stride):
     return views + [(num_frames - window_size + 1, num_frames)]
 
 
+WindowLayout = collections.namedtuple("WindowLayout", "framepar wpar world rank nslots slot")
+
+
+def window_layout(parallel, window_size):
+    """Several windows, four ways to spread them (the pipeline's ``parallel``; parallel.window_layout_costs prices them):
+      None            every window on this GPU, one after the other;
+      WindowParallel  the distinct windows of a step dealt to the ranks, one all-gather per round;
+      FrameParallel   (Layout of window_size frames) every window on ALL ranks, 2-way CFG x frame shards inside the
+                      window, the stepped window gathered before the overlap average -- the layout for more ranks than
+                      windows (on 8 ranks and 7 windows WindowParallel's single round is the faster of the two);
+      GroupedWindowParallel  G groups of g ranks: windows dealt to the groups, frame-parallel inside a group.
+    In all of them every rank holds all N latent frames and applies the same overlap average in view order.
+    -> framepar: what shards the frames of a window, or None; wpar: what deals the windows, or None; world, rank: over which
+    ranks the VAE chunks are dealt; nslots, slot: the windows of a round and which of them this rank steps."""
+    from .parallel import FrameParallel, GroupedWindowParallel
+    grouped = parallel if isinstance(parallel, GroupedWindowParallel) else None
+    framepar = parallel if isinstance(parallel, FrameParallel) else (grouped.frame if grouped is not None else None)
+    wpar = grouped if grouped is not None else (parallel if framepar is None else None)
+    if wpar is not None:                                              # (world, rank global: VAE chunks go to all ranks)
+        return WindowLayout(framepar, wpar, wpar.world, wpar.rank, len(wpar.rounds([None])[0]), wpar.slot)
+    sh = _Shard(framepar, window_size)
+    return WindowLayout(framepar, None, sh.world, sh.rank, 1, 0)
+
+
+class WindowPlan:
+    """The overlap average of one denoise step over ``views`` (svdxt_pipeline_ctrlnet_loop.py:502-511) as tables, no tensors:
+    ``value[0:t1] += window`` for the first view, ``value[t0:t1] += window[1:]`` for the others, in view order, then
+    ``latents = value / count``.  ``count[f]`` = the views that cover frame f (a repeated view counts again)."""
+
+    def __init__(self, views, num_frames, decode_chunk_size):
+        if views[0][0] != 1:
+            raise ValueError("the first window must start at frame 1")
+        self.views, self.N, self.chunk = list(views), num_frames, decode_chunk_size
+        self.nchunks = -(-num_frames // decode_chunk_size)
+        self.count, self.last_view_of, self.adds = [0] * num_frames, [-1] * num_frames, []
+        for idx, (t0, t1) in enumerate(self.views):
+            dst0, src0 = (0, 0) if idx == 0 else (t0, 1)
+            self.adds.append([(idx, src0 + k, dst0 + k, self.count[dst0 + k] == 0) for k in range(t1 - dst0)])
+            for f in range(dst0, t1):
+                self.count[f] += 1
+                self.last_view_of[f] = idx            # the last covering view in processing order: f is final once it is merged
+
+    def accumulations(self, m, since=0):
+        """what merging the views [since, m) issues, in order: (view, row of its window, frame, first touch of that frame?)"""
+        return [a for adds in self.adds[since:m] for a in adds]
+
+    def frontier(self, m):
+        """with the views [0, m) merged the frames [0, frontier) are final: their last covering view is among them"""
+        f = 0
+        while f < self.N and self.last_view_of[f] < m:
+            f += 1
+        return f
+
+    def ready_chunks(self, m):
+        """the decode chunks that lie wholly below ``frontier(m)``"""
+        F = self.frontier(m)
+        return [ci for ci in range(self.nchunks) if min((ci + 1) * self.chunk, self.N) <= F]
+
+
+class _WindowLoop:
+    """One call of the window loop: the stepped windows of a timestep are averaged into ``lat`` fp32 [N,4,h,w] as ``plan`` says.
+    windows: {view: (its adapters, its UNet Ctx)} of the DISTINCT views, in view order; step: the ``_Step`` of a window."""
+
+    def __init__(self, pipe, lo, views, plan, step, windows, lat, overlap_decode):
+        self.pipe, self.lo, self.views, self.plan, self.step, self.windows, self.lat = pipe, lo, views, plan, step, windows, lat
+        self.value = torch.empty_like(lat)
+        self.rounds = lo.wpar.rounds(list(windows)) if lo.wpar is not None else [[k] for k in windows]
+        # the decode of finished frames overlaps the rest of the LAST step on a second HIP stream wherever that step has more
+        # than one round; a chunk belongs to ``owner[ci]`` (the same table on every rank)
+        self.side = torch.cuda.Stream(device=pipe.device) if (overlap_decode and len(self.rounds) > 1) else None
+        self.stream_chunks, self.owner = {}, {}
+
+    def step_window(self, lat_in, view, scal):
+        """-> the window ``view`` of ``lat_in`` after one step, all its frames [Tw,4,h,w]"""
+        sh = self.step.sh
+        lw = torch.cat([lat_in[0:1], lat_in[view[0]:view[1]]], dim=0)             # frame 0 + window frames
+        lw = lw[sh.f0:sh.f1].contiguous()                                         # (this rank's frames of the window)
+        self.step(lw, scal, *self.windows[view])
+        return sh.gather(lw, self.step.h, self.step.w)
+
+    def step_round(self, lat_in, rnd, scal, done):
+        wpar = self.lo.wpar
+        if wpar is None:
+            done[rnd[0]] = self.step_window(lat_in, rnd[0], scal)
+            return
+        mine = rnd[self.lo.slot]                                  # window-parallel: one window per rank and round
+        lw = self.step_window(lat_in, mine, scal) if mine is not None else \
+            torch.zeros((self.step.sh.T,) + tuple(self.lat.shape[1:]), dtype=self.lat.dtype, device=self.lat.device)
+        for key, got in zip(rnd, wpar.gather(lw)):
+            if key is not None:
+                done[key] = got
+
+    def merge(self, m0, m1, done):
+        """value[0:t1] += lw (first view) / value[t0:t1] += lw[1:] (others)   (:502-507)"""
+        for idx, src, f, first in self.plan.accumulations(m1, since=m0):
+            ops.axpby_f32_(done[self.views[idx]][src].reshape(-1), self.value[f].reshape(-1), 1.0, 0.0 if first else 1.0)
+
+    def finalize(self, frames):
+        """latents = where(count > 0, value / count, value) (:511; value is 0 where no window landed)"""
+        for f in frames:
+            if self.plan.count[f]:
+                ops.axpby_f32_(self.value[f].reshape(-1), self.lat[f].reshape(-1), 1.0 / self.plan.count[f], 0.0)
+            else:
+                self.lat[f].zero_()
+
+    def decode_on_side(self, chunks):
+        """the VAE decode of the (final) frames of ``chunks`` on the second stream, behind everything enqueued so far"""
+        vae, n, lat_r = self.pipe.vae, self.plan.chunk, self.pipe._round(self.lat)
+        ev = torch.cuda.Event()
+        ev.record()
+        with torch.cuda.stream(self.side):
+            self.side.wait_event(ev)
+            lat_r.record_stream(self.side)                        # (lat_r may be a temporary of the main stream: keep its
+            for ci in chunks:                                     #  block out of the allocator until the decode ran)
+                z = lat_r[ci * n:min(ci * n + n, self.plan.N)]
+                self.stream_chunks[ci] = vae.decode(z, num_frames=z.shape[0], _prescale=1.0 / vae.config.scaling_factor)
+
+    def deal_ready(self, merged, next_round):
+        """-> the chunks that became final with the views [0, merged) and are this rank's to decode while ``next_round`` runs"""
+        lo = self.lo
+        ready = [ci for ci in self.plan.ready_chunks(merged) if ci not in self.owner]
+        busy_next = [r for r in range(lo.world) if lo.wpar is None or next_round[r * lo.nslots // lo.world] is not None]
+        for ci, r in _deal_ready_chunks(ready, lo.world, busy_next):
+            self.owner[ci] = r
+        return [ci for ci in ready if self.owner.get(ci) == lo.rank]
+
+    def run_step(self, scal, overlap):
+        views, plan, done = self.views, self.plan, {}
+        # every window of a step reads the latents of the PREVIOUS step; when frames are finalised while later windows
+        # of the (last) step still run, those windows read a snapshot
+        lat_in = self.lat.clone() if overlap else self.lat
+        merged, frontier = 0, 0                               # views [0, merged) are merged, frames [0, frontier) final
+        for ri, rnd in enumerate(self.rounds):
+            self.step_round(lat_in, rnd, scal, done)
+            if not overlap or ri == len(self.rounds) - 1:
+                continue
+            # views are merged in view order as soon as their window is stepped (the same summation order as after the
+            # loop); every frame whose last covering view is merged can be averaged now, and whole decode chunks below
+            # the frontier go to the second stream while the next round runs
+            m = merged
+            while m < len(views) and views[m] in done:
+                m += 1
+            self.merge(merged, m, done)
+            newf = plan.frontier(m)
+            self.finalize(range(frontier, newf))
+            merged, frontier = m, newf
+            mine = self.deal_ready(merged, self.rounds[ri + 1])
+            if mine:
+                self.decode_on_side(mine)
+        self.merge(merged, len(views), done)
+        self.finalize(range(frontier, plan.N))
+
+    def run(self, callback):
+        """every timestep of the scheduler -> (latents, {chunk: its rank}, {chunk: frames already decoded})"""
+        pipe, sch = self.pipe, self.pipe.scheduler
+        n = pipe._num_timesteps = len(sch.timesteps)
+        for i, t in enumerate(sch.timesteps):
+            self.run_step((t, *sch.sigma_pair(i)), overlap=(i == n - 1 and self.side is not None))
+            self.lat = pipe._callback(callback, i, t, pipe._round(self.lat), (1,) + tuple(self.lat.shape))
+        if self.side is not None:
+            torch.cuda.current_stream().wait_stream(self.side)
+            if callback is not None:
+                self.stream_chunks, self.owner = {}, {}   # a callback may have replaced the latents after the last step
+        rest = [ci for ci in range(self.plan.nchunks) if ci not in self.owner]   # the chunks still to decode: dealt evenly
+        for j, ci in enumerate(rest):
+            self.owner[ci] = j % self.lo.world
+        return self.lat, self.owner, self.stream_chunks
+
+
 class KeypointFlowControlNetPipeline(FlowControlNetPipeline):
     """The window loop of the reference's long-video pipeline.  Two extensions beyond it (new work, BASELINE config 5):
     * hybrid control inside the windows: built with a ``drag_controlnet`` and called with ``drag_flow`` / ``mask``, every
@@ -599,28 +774,13 @@ class KeypointFlowControlNetPipeline(FlowControlNetPipeline):
         self.drag_controlnet = drag_controlnet
         self.overlap_decode = overlap_decode
 
-    def _single_window_sharded(self, lat, il, emb, cond, flow, dflow, landmarks, mask, timesteps, h, w, height, width, gmin, gmax,
-                               cn_scale, traj_scale, callback):
-        """the window loop for ONE window == the clip, on this rank's CFG half / frame shard (see __call__)"""
-        unet, cn, drag, sch, dev = self.unet, self.controlnet, self.drag_controlnet, self.scheduler, self.device
-        T = lat.shape[0]
-        sh = _Shard(self.parallel, T)
-        f0, f1, Tl, Bl, half, fpar = sh.f0, sh.f1, sh.Tl, sh.Bl, sh.half, sh.fpar
-        hybrid = dflow is not None
-        # window = frame 0 + frames 1 .. T-1 with the flows of frames 1 .. T-1 (svdxt_pipeline_ctrlnet_loop.py:470-476)
-        cf = cn.prepare_condition(cond[:1], flow[:1, 0:T - 1], landmarks[:, 0:T], frames=(f0, f1))
-        cd = drag.prepare_condition(cond[:1], dflow[:1, 0:T - 1], frames=(f0, f1)) if hybrid else None
-        masks = _resized_masks(mask, height, width, h, w, dev) if hybrid else None
-        lat = lat[f0:f1].contiguous()
-        gspan = (gmax - gmin) / max(T - 1, 1)
-        g0, g1 = gmin + gspan * f0, gmin + gspan * (f1 - 1)
-        added_time_ids = torch.tensor([[6.0, 128.0, 0.02]] * 2, dtype=torch.float32, device=dev)
-        c_f, c_d, c_u = Ctx(Bl, Tl), Ctx(Bl, Tl), Ctx(Bl, Tl)
-        adapters = [(cn, c_f, cf, cn_scale)] + ([(drag, c_d, cd, traj_scale)] if hybrid else [])
-        lat = self._clip_loop(lat, il, emb, added_time_ids, adapters, c_u, masks, sh, h, w, g0, g1, callback)
-        if fpar is not None:
-            lat = fpar.gather_frames(lat.reshape(Tl, 4 * h * w), 1).reshape(T, 4, h, w)
-        return lat
+    def _check_windows(self, Tw, stride, hybrid, mask, N):
+        if N < Tw:
+            raise ValueError(f"num_frames ({N}) must be at least window_size ({Tw})")
+        if not 0 < stride < Tw:
+            raise ValueError(f"stride ({stride}) must lie in (0, window_size = {Tw}): consecutive windows have to overlap")
+        if hybrid and (self.drag_controlnet is None or mask is None):
+            raise ValueError("hybrid control needs a drag_controlnet (constructor) and a mask")
 
     @torch.no_grad()
     def __call__(self, image=None, controlnet_condition=None, controlnet_flow=None, landmarks=None, window_size: int = 25,
@@ -632,195 +792,45 @@ class KeypointFlowControlNetPipeline(FlowControlNetPipeline):
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs: List[str] = ["latents"],
                  return_dict: bool = True, controlnet_cond_scale=1.0, batch_size=1, *, image_embeddings=None,
                  image_latents=None, drag_flow=None, mask=None, ctrl_scale_traj=1.0):
-        unet, cn, drag, sch, dev = self.unet, self.controlnet, self.drag_controlnet, self.scheduler, self.device
-        N = num_frames if num_frames is not None else unet.config.num_frames
-        Tw = window_size
-        decode_chunk_size = decode_chunk_size if decode_chunk_size is not None else N
-        self.check_inputs(image, height, width)
-        self._check_call(batch_size, num_videos_per_prompt, max_guidance_scale, Tw)
-        if N < Tw:
-            raise ValueError(f"num_frames ({N}) must be at least window_size ({Tw})")
-        if not 0 < stride < Tw:
-            raise ValueError(f"stride ({stride}) must lie in (0, window_size = {Tw}): consecutive windows have to overlap")
-        hybrid = drag_flow is not None
-        if hybrid and (drag is None or mask is None):
-            raise ValueError("hybrid control needs a drag_controlnet (constructor) and a mask")
-        h, w = height // 8, width // 8
-        emb, il = self._conditioning(image, image_embeddings, image_latents, height, width, noise_aug_strength, generator)
-        sch.set_timesteps(num_inference_steps)
-        timesteps = sch.timesteps
-        lat = self.prepare_latents(1, N, unet.config.in_channels, height, width, generator, latents).reshape(N, 4, h, w).contiguous()
-        cond = self._condition_image(controlnet_condition, height, width)
+        cn, drag, dev = self.controlnet, self.drag_controlnet, self.device
+        Tw, hybrid = window_size, drag_flow is not None
+        N, decode_chunk_size, h, w, emb, il, lat, cond = self._prologue(
+            image, height, width, num_frames, Tw, decode_chunk_size, batch_size, num_videos_per_prompt, max_guidance_scale,
+            num_inference_steps, noise_aug_strength, generator, latents, image_embeddings, image_latents, controlnet_condition,
+            more_checks=functools.partial(self._check_windows, Tw, stride, hybrid, mask))
         flow = controlnet_flow.to(dev, torch.float32)
         dflow = drag_flow.to(dev, torch.float32) if hybrid else None
+        masks = _resized_masks(mask, height, width, h, w, dev) if hybrid else None
         views = window_views(N, Tw, stride)
-        from .parallel import FrameParallel, GroupedWindowParallel
-        grouped = self.parallel if isinstance(self.parallel, GroupedWindowParallel) else None
-        framepar = self.parallel if isinstance(self.parallel, FrameParallel) else (grouped.frame if grouped is not None else None)
-        if framepar is not None and grouped is None and len(set(views)) == 1 and N == Tw:
+        lo = window_layout(self.parallel, Tw)
+        sh = _Shard(lo.framepar, Tw)
+        fr = dict(frames=(sh.f0, sh.f1)) if lo.framepar is not None else {}
+        if lo.framepar is not None and lo.wpar is None and len(set(views)) == 1 and N == Tw:
             # ONE window that is the whole clip (N == window_size: every view is frames 1 .. N-1 behind frame 0): the loop
             # degenerates to the plain denoise loop -- value = k * stepped window, count = k -- so the clip is frame-sharded
             # exactly like FlowControlNetPipeline / HybridFlowControlNetPipeline (2-way CFG x frame shards) and the latents
             # stay sharded between the steps.
-            lat = self._single_window_sharded(lat, il, emb, cond, flow, dflow, landmarks, mask, timesteps, h, w, height, width,
-                                              min_guidance_scale, max_guidance_scale, controlnet_cond_scale, ctrl_scale_traj,
-                                              callback_on_step_end)
-            sh = _Shard(self.parallel, N)
-            frames = self._decode(lat.reshape(1, N, 4, h, w), N, decode_chunk_size, output_type, sh)
-            if not return_dict:
-                return frames, controlnet_flow
-            return FlowControlNetPipelineOutput(frames=frames, controlnet_flow=controlnet_flow)
-        # Several windows, four ways to spread them (self.parallel; parallel.window_layout_costs prices them):
-        #   None            every window on this GPU, one after the other;
-        #   WindowParallel  the distinct windows of a step dealt to the ranks, one all-gather per round;
-        #   FrameParallel   (Layout of window_size frames) every window on ALL ranks, 2-way CFG x frame shards inside the
-        #                   window, the stepped window gathered before the overlap average -- the layout for more ranks than
-        #                   windows (on 8 ranks and 7 windows WindowParallel's single round is the faster of the two);
-        #   GroupedWindowParallel  G groups of g ranks: windows dealt to the groups, frame-parallel inside a group.
-        # In all of them every rank holds all N latent frames and applies the same overlap average in view order.
-        sh_w = _Shard(framepar, Tw)
-        f0, f1, Tl, Bl, half, fpar = sh_w.f0, sh_w.f1, sh_w.Tl, sh_w.Bl, sh_w.half, sh_w.fpar
+            # window = frame 0 + frames 1 .. N-1 with the flows of frames 1 .. N-1 (svdxt_pipeline_ctrlnet_loop.py:470-476)
+            networks = [(cn, cn.prepare_condition(cond[:1], flow[:1, 0:N - 1], landmarks[:, 0:N], **fr), controlnet_cond_scale)]
+            if hybrid:
+                networks.append((drag, drag.prepare_condition(cond[:1], dflow[:1, 0:N - 1], **fr), ctrl_scale_traj))
+            lat = self._run_clip(sh, lat, il, emb, networks, masks, h, w, min_guidance_scale, max_guidance_scale, callback_on_step_end)
+            return self._epilogue(lat, decode_chunk_size, output_type, return_dict, controlnet_flow, sh.world, sh.rank)
         # adapter state per DISTINCT window is timestep-invariant: computed once per clip (the reference recomputes it
         # every step; its last view often repeats the previous one -- SURVEY 3.5 -- and is computed once here)
-        conds, dconds = {}, {}
-        fr = dict(frames=(f0, f1)) if framepar is not None else {}
+        windows = {}
         for (t0, t1) in views:
-            if (t0, t1) not in conds:
-                lm = torch.cat([landmarks[:, 0:1], landmarks[:, t0:t1]], dim=1)
-                conds[(t0, t1)] = cn.prepare_condition(cond[:1], flow[:1, t0 - 1:t1 - 1], lm, **fr)
-                if hybrid:
-                    dconds[(t0, t1)] = drag.prepare_condition(cond[:1], dflow[:1, t0 - 1:t1 - 1], **fr)
-        masks = _resized_masks(mask, height, width, h, w, dev) if hybrid else None
-        added_time_ids = torch.tensor([[6.0, 128.0, 0.02]] * 2, dtype=torch.float32, device=dev)
-        ctxs = {v: (Ctx(Bl, Tl), Ctx(Bl, Tl), Ctx(Bl, Tl)) for v in conds}
-        distinct = list(conds)                                                     # distinct windows, in view order
-        wpar = grouped if grouped is not None else (self.parallel if framepar is None else None)   # deals windows, or None
-        if wpar is not None:
-            world, rank = wpar.world, wpar.rank                                    # (global: VAE chunks go to all ranks)
-        else:
-            world, rank = (sh_w.world, sh_w.rank) if framepar is not None else (1, 0)
-        nslots, slot = (len(wpar.rounds(list(conds))[0]), wpar.slot) if wpar is not None else (1, 0)
-        rows = Tl * h * w
-        x_in = torch.zeros((2 * rows, unet.in_ld), dtype=torch.float16, device=dev)
-        x_loc = x_in if Bl == 2 else x_in[half * rows:(half + 1) * rows]
-        g0, g1 = min_guidance_scale, max_guidance_scale
-        if framepar is not None:                                                   # guidance of this rank's frames of a window
-            gspan = (max_guidance_scale - min_guidance_scale) / max(Tw - 1, 1)
-            g0, g1 = min_guidance_scale + gspan * f0, min_guidance_scale + gspan * (f1 - 1)
-        value = torch.empty_like(lat)
-        # the views that cover each frame, and the last of them in processing order: a frame is final once that one is merged
-        last_view_of = [max(idx for idx, (t0, t1) in enumerate(views) if (0 if idx == 0 else t0) <= f < t1) for f in range(N)]
-        nchunks = -(-N // decode_chunk_size)
-        rounds = wpar.rounds(distinct) if wpar is not None else [[k] for k in distinct]
-        # the decode of finished frames overlaps the rest of the LAST step on a second HIP stream wherever that step has more
-        # than one round; a chunk belongs to ``owner[ci]`` (the same table on every rank)
-        side = torch.cuda.Stream(device=dev) if (self.overlap_decode and output_type != "latent" and len(rounds) > 1) else None
-        stream_chunks, owner = {}, {}
-        self._num_timesteps = len(timesteps)
-        for i, t in enumerate(timesteps):
-            sigma, sigma_next = sch.sigma_pair(i)
-            overlap = i == len(timesteps) - 1 and side is not None
-            count = [0] * N
-            touched = [False] * N
-            # every window of a step reads the latents of the PREVIOUS step; when frames are finalised while later windows
-            # of the (last) step still run, those windows read a snapshot
-            lat_in = lat.clone() if overlap else lat
-
-            def step_window(t0, t1):
-                lw = torch.cat([lat_in[0:1], lat_in[t0:t1]], dim=0)                   # frame 0 + window frames
-                lw = lw[f0:f1].contiguous()                                           # (this rank's frames of the window)
-                ops.prepare_model_input(lw, il, x_in, sigma)
-                c_cn, c_dr, c_un = ctxs[(t0, t1)]
-                adapters = [(cn, c_cn, conds[(t0, t1)], controlnet_cond_scale)]
-                if hybrid:
-                    adapters.append((drag, c_dr, dconds[(t0, t1)], ctrl_scale_traj))
-                noise = self._denoise_forward(x_loc, t, emb, added_time_ids, Bl, Tl, half, fpar, h, w, adapters, c_un, masks)
-                if Bl == 1:
-                    noise = framepar.gather_cfg(noise)
-                ops.cfg_euler_step_(lw, noise, sigma, sigma_next, g0, g1)
-                if fpar is not None:
-                    lw = fpar.gather_frames(lw.reshape(Tl, 4 * h * w), 1).reshape(Tw, 4, h, w)
-                return lw
-
-            def merge(idx, lw):
-                """value[0:t1] += lw (first view) / value[t0:t1] += lw[1:] (others)   (:502-507)"""
-                t0, t1 = views[idx]
-                if idx == 0 and t0 != 1:
-                    raise ValueError("the first window must start at frame 1")
-                dst0, src0 = (0, 0) if idx == 0 else (t0, 1)
-                for k in range(t1 - dst0):
-                    f = dst0 + k
-                    ops.axpby_f32_(lw[src0 + k].reshape(-1), value[f].reshape(-1), 1.0, 1.0 if touched[f] else 0.0)
-                    touched[f] = True
-                    count[f] += 1
-
-            def finalize(frames):
-                """latents = where(count > 0, value / count, value) (:511; value is 0 where no window landed)"""
-                for f in frames:
-                    if count[f]:
-                        ops.axpby_f32_(value[f].reshape(-1), lat[f].reshape(-1), 1.0 / count[f], 0.0)
-                    else:
-                        lat[f].zero_()
-
-            done = {}
-            merged, frontier = 0, 0                               # views [0, merged) are merged, frames [0, frontier) final
-            for ri, rnd in enumerate(rounds):
-                if wpar is None:
-                    done[rnd[0]] = step_window(*rnd[0])
-                else:                                             # window-parallel: one window per rank and round
-                    mine = rnd[slot]
-                    lw = step_window(*mine) if mine is not None else torch.zeros((Tw,) + tuple(lat.shape[1:]),
-                                                                                dtype=lat.dtype, device=dev)
-                    for key, got in zip(rnd, wpar.gather(lw)):
-                        if key is not None:
-                            done[key] = got
-                if not overlap or ri == len(rounds) - 1:
-                    continue
-                # views are merged in view order as soon as their window is stepped (the same summation order as after the
-                # loop); every frame whose last covering view is merged can be averaged now, and whole decode chunks below
-                # the frontier go to the second stream while the next round runs
-                while merged < len(views) and views[merged] in done:
-                    merge(merged, done[views[merged]])
-                    merged += 1
-                newf = frontier
-                while newf < N and last_view_of[newf] < merged:
-                    newf += 1
-                finalize(range(frontier, newf))
-                frontier = newf
-                ready = [ci for ci in range(nchunks) if ci not in owner and min((ci + 1) * decode_chunk_size, N) <= frontier]
-                busy_next = [r for r in range(world) if wpar is None or rounds[ri + 1][r * nslots // world] is not None]
-                for ci, r in _deal_ready_chunks(ready, world, busy_next):
-                    owner[ci] = r
-                mine = [ci for ci in ready if owner.get(ci) == rank]
-                if mine:
-                    lat_r = self._round(lat)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    with torch.cuda.stream(side):
-                        side.wait_event(ev)
-                        lat_r.record_stream(side)                 # (lat_r may be a temporary of the main stream: keep its
-                        for ci in mine:                           #  block out of the allocator until the decode ran)
-                            s0 = ci * decode_chunk_size
-                            z = lat_r[s0:min(s0 + decode_chunk_size, N)]
-                            stream_chunks[ci] = self.vae.decode(z, num_frames=z.shape[0],
-                                                                _prescale=1.0 / self.vae.config.scaling_factor)
-            while merged < len(views):
-                merge(merged, done[views[merged]])
-                merged += 1
-            finalize(range(frontier, N))
-            lat = self._round(lat)
-            lat = self._callback(callback_on_step_end, i, t, lat, (1, N, 4, h, w))
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-            if callback_on_step_end is not None:
-                stream_chunks, owner = {}, {}             # a callback may have replaced the latents after the last step
-        rest = [ci for ci in range(nchunks) if ci not in owner]   # the chunks still to decode: dealt evenly
-        for j, ci in enumerate(rest):
-            owner[ci] = j % world
-        sh = _Shard(None, N)
-        sh.world, sh.rank = world, rank
-        sh.owner = owner
-        frames = self._decode(lat.reshape(1, N, 4, h, w), N, decode_chunk_size, output_type, sh, stream_chunks)
-        if not return_dict:
-            return frames, controlnet_flow
-        return FlowControlNetPipelineOutput(frames=frames, controlnet_flow=controlnet_flow)
+            if (t0, t1) in windows:
+                continue
+            lm = torch.cat([landmarks[:, 0:1], landmarks[:, t0:t1]], dim=1)
+            adapters = [(cn, Ctx(sh.Bl, sh.Tl), cn.prepare_condition(cond[:1], flow[:1, t0 - 1:t1 - 1], lm, **fr), controlnet_cond_scale)]
+            if hybrid:
+                adapters.append((drag, Ctx(sh.Bl, sh.Tl), drag.prepare_condition(cond[:1], dflow[:1, t0 - 1:t1 - 1], **fr), ctrl_scale_traj))
+            windows[(t0, t1)] = (adapters, Ctx(sh.Bl, sh.Tl))
+        gmin, gmax = min_guidance_scale, max_guidance_scale
+        g0, g1 = sh.guidance(gmin, gmax) if lo.framepar is not None else (gmin, gmax)   # of this rank's frames of a window
+        step = _Step(self, sh, il, emb, [cn] + ([drag] if hybrid else []), masks, h, w, g0, g1)
+        loop = _WindowLoop(self, lo, views, WindowPlan(views, N, decode_chunk_size), step, windows, lat,
+                           self.overlap_decode and output_type != "latent")
+        lat, owner, stream_chunks = loop.run(callback_on_step_end)
+        return self._epilogue(lat, decode_chunk_size, output_type, return_dict, controlnet_flow, lo.world, lo.rank, owner, stream_chunks)

@@ -8,7 +8,7 @@ entry the pipeline uses (token-major fp16 in/out).
 import torch
 
 from . import ops
-from .blocks import BIG, Conv3x3, Ctx, DownBlock, GroupNorm, MidBlock, Sub, TembBatch, TimeEmbedding, UpBlock, drive
+from .blocks import BIG, Conv3x3, DownBlock, GroupNorm, MidBlock, Sub, TembBatch, TimeEmbedding, UpBlock, drive, make_ctx
 
 SVD_XT_HEADS = (5, 10, 20, 20)
 DEFAULT_CONFIG = dict(in_channels=8, out_channels=4, block_out_channels=(320, 640, 1280, 1280),
@@ -78,27 +78,7 @@ class UNetSpatioTemporalConditionControlNetModel:
 
     # ------------------------------------------------------------------------------------------------
     def make_ctx(self, timestep, encoder_hidden_states, added_time_ids, B, T, base=None, half=None, par=None):
-        """B, T = LOCAL batch / frame counts.  half: global CFG-half index when this rank computes one half only
-        (encoder_hidden_states / added_time_ids are then still the global 2-row tensors); par: FrameParallel."""
-        c = base if base is not None else Ctx(B, T)
-        ts = torch.as_tensor(timestep, dtype=torch.float32, device=self.device).reshape(-1)
-        ts = ts.expand(B).contiguous() if ts.numel() == 1 else ts.contiguous()
-        ids = added_time_ids.to(self.device, torch.float32)
-        if half is not None:
-            ids = ids[half:half + B]
-        c.temb_act = self.time(ts, ids.contiguous())
-        c.temb_all = self.temb_batch.run(c.temb_act)
-        if c.ctx16 is None:
-            e = encoder_hidden_states.to(self.device, torch.float32)
-            e = e.reshape(e.shape[0], -1).contiguous()
-            if half is not None:
-                c.ctx16_all = ops.cast_f32_to_f16(e)
-                c.ctx16 = c.ctx16_all[half:half + B].contiguous()
-                c.half = half
-            else:
-                c.ctx16 = ops.cast_f32_to_f16(e)
-        c.par = par
-        return c
+        return make_ctx(self, timestep, encoder_hidden_states, added_time_ids, B, T, base, half, par)   # blocks.make_ctx
 
     def forward_tokens(self, x, c, H, W, down_res, mid_res):
         """x: fp16 [B*T*H*W, in_ld] (channels >= in_channels zero); down_res: 12 token tensors; mid_res: token

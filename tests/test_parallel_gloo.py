@@ -234,7 +234,7 @@ def _block_worker(rank, world, port, T, HW, C, two_networks):
                 errs = blocks.drive(network(7, 3, []))
                 assert max(errs) < 2e-2, (rank, split, errs)
         else:
-            # two networks of different length enqueued in lockstep by ONE thread, as pipeline._denoise_forward_sharded does:
+            # two networks of different length enqueued in lockstep by ONE thread, as pipeline._denoise_forward does:
             # every rank issues the same sequence of exchanges whatever its host timing is (the ranks are delayed differently)
             par.log = []
 
