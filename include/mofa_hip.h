@@ -231,7 +231,8 @@ int mofa_layernorm_f16(const void* x, const float* gamma, const float* beta, voi
  *   w2p  fp16 [40 chunks][10 out tiles][2 k-steps][64 lanes][8]: element jj of lane l = net.2.weight[32 j + (l & 31)]
  *        [32 c + 16 u + 4 (l >> 5) + (jj & 3) + 8 (jj >> 2)]
  *   b2   fp32 [320]
- * All pointers 16-byte aligned, ld* % 8 == 0.  fp16 MFMA, fp32 accumulation / LayerNorm / GELU / residual arithmetic. */
+ * All pointers 16-byte aligned, ld* % 8 == 0.  fp16 MFMA, fp32 accumulation / LayerNorm / GELU / residual arithmetic.
+ * tests/test_l0_matrix_gpu.py runs the row edges, three tiles per workgroup on periodic rows and poisoned rows. */
 typedef struct mofa_ff320_args {
     const void* x;          /* fp16 [M][ldx]                                    */
     const float* pos;       /* fp32 [T][320] or NULL                            */
@@ -262,7 +263,8 @@ int mofa_ff320_f16(const mofa_ff320_args* a, mofa_stream_t stream);
  * W'[64 c + 32 t + (l & 31)][16 s + 8 (l >> 5) + e], W' = W * LayerNorm gain (mofa_video_amd/weights.py::pack_lin320);
  * bias fp32 [N] (+ W . LayerNorm bias) or NULL.  Pointers 16-byte aligned, ld* % 8 == 0.  The output is addressed through a 32-bit
  * buffer descriptor (rows beyond M are dropped by its bounds check): (M + 256) * ldo * 2 bytes must stay below 4 GB, MOFA_EINVAL
- * otherwise (the caller then uses mofa_layernorm_f16 + mofa_igemm_f16: mofa_video_amd/ops.py::lin320_fits). */
+ * otherwise (the caller then uses mofa_layernorm_f16 + mofa_igemm_f16: mofa_video_amd/ops.py::lin320_fits).
+ * tests/test_l0_matrix_gpu.py holds all eight instances to the two roundings above bit for bit, on exactly representable sums. */
 typedef struct mofa_lin320_args {
     const void* x;          /* fp16 [M][ldx], 320 channels                      */
     const void* wp;         /* packed, see above                                */
