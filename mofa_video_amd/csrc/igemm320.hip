@@ -8,18 +8,26 @@
 // one output row), buffer-descriptor DMA with bounds-check zero fill, persistent XCD-aware tile walk and two-wave-group
 // stagger as igemm8.hip; what differs:
 //
-//   * wave (wm, wn) of 4 x 2 owns 64 (M) x 160 (N) outputs = 2 x 5 accumulator tiles of 32x32 (160 accumulator registers).
+//   * wave (wm, wn) of 4 x 2 owns 64 (M) x 160 (N) outputs = 2 x 5 accumulator blocks of 32x32 (160 accumulator registers).
 //     A K tile (64 deep) is consumed in TWO PHASES BY K HALVES: phase p multiplies K columns [32 p, 32 p + 32) of all the
-//     wave's rows -- 4 X + 10 W fragment reads (56 registers), 20 MFMAs (640 matrix-pipe cycles) -- so both phases carry
+//     wave's rows -- 4 X + 10 W fragment reads (56 registers), 40 MFMAs (640 matrix-pipe cycles) -- so both phases carry
 //     the same reads and the same MFMA count (the 256x256 kernel splits by X rows: 16 + 8 reads).
+//   * the K loop runs on v_mfma_f32_16x16x32_f16: a K half is ONE K step of that shape, each fragment (16 rows x 32 K) one
+//     ds_read_b128, each 32x32 block four 16x16 tiles in the quarters of its 16 registers.  Same reads, same matrix-pipe
+//     cycles and -- measured -- the same bits as two 32x32x16 steps, but the power-limited chip holds a higher clock on this
+//     shape (tools/lds_mfma_bench.hip, profiles/igemm320_k16_loop_bench.log: + 14 % bare, + 7 % beside the DMA issue;
+//     tile bench + 5-9 % on the deep-K shapes, clip + 2.1 %: profiles/igemm320_k16_*.log).  The W rows of a fragment are read
+//     in an order (bits 2 and 3 of the row swapped) that makes 80 v_permlane16_swap_b32 per tile turn the accumulators into
+//     the 32x32 register layout (to_layout32); every epilogue, the split-K dump and the GroupNorm sums work on that layout.
 //   * LDS: a ring of 2 K tiles, each as two K-HALF PLANES [X 256 rows | W 320 rows] x 64 B (36 KB per plane, 72 KB per K
 //     tile, 144 KB ring + 8 x 2 KB wave scratch = the CU's 160 KB).  A plane is released when its phase's fragments are in
 //     registers and refilled in the NEXT phase: phase 0 issues plane 1 of K tile t + 1, phase 1 issues plane 0 of K tile
 //     t + 2 -- 4 or 5 DMA pieces per wave and phase (9 per K tile; waves 0-3 take the ring's 4 odd W pieces in plane 0,
 //     waves 4-7 in plane 1), each with one K tile of flight before the counted wait `vmcnt(9)`.  A DMA piece is 16 rows x
 //     64 B (tools/dmabench.hip, profiles/archive/r03_dmabench.log: up to 5 such half-line pieces per phase hide completely behind
-//     20 MFMAs of the partner wave; 6 do not).  64-byte rows: the 16-byte chunk c of row r sits in slot c ^ ((r >> 2) & 3)
-//     (applied to the DMA source address and to the fragment read; tools/lds_bank_sim.py: conflict-free).
+//     20 32x32x16 MFMAs of the partner wave; 6 do not).  64-byte rows: the 16-byte chunk c of row r sits in slot
+//     c ^ slot_swz((r >> 2) & 3) (applied to the DMA source address and to the fragment read; tools/lds_bank_sim.py:
+//     conflict-free for the 16-row fragment reads; the plain c ^ ((r >> 2) & 3) of the 32-row reads is 2-way on them).
 //   * bias (and the row vector when the wave's 64 rows share one row of it: every tile that does not straddle a frame) is
 //     the INITIAL VALUE of the accumulators -- no bias handling in any epilogue.  The bias arrives through LDS one tile
 //     ahead (LDS-DMA into a 768-byte slot per wave and tile parity), the uniform row-vector row by global loads.
@@ -50,6 +58,12 @@ constexpr int LOOKAHEAD3 = 4 + NJ3;                            // DMA instructio
 
 // epilogue scratch row r (128 bytes) of a wave: rows 8 b .. 8 b + 7 in its 1 KB block b, the blocks 8 KB apart (see the kernel)
 struct ScratchRows { __device__ __forceinline__ int operator()(int r) const { return (r >> 3) * 8192 + (r & 7) * 128; } };
+
+// slot swizzle of the K-half planes: the 16-byte chunk c of row r sits in slot c ^ slot_swz((r >> 2) & 3) = c ^ {0, 3, 2, 1}.  A
+// ds_read_b128 is served in four groups of 16 lanes (0-3 12-15 20-27 | 4-11 16-19 28-31 | + 32); with lane l on row l & 15, chunk
+// l >> 4, a group holds rows {0-3, 12-15} of one chunk and rows 4-11 of its neighbour: the four row quads need four different slots
+// (the plain c ^ ((r >> 2) & 3) puts quads 0 and 1, 2 and 3 on the same banks: 2-way).  tools/lds_bank_sim.py: conflict-free.
+__device__ __forceinline__ int slot_swz(int q) { return q ^ ((q & 1) << 1); }
 
 struct Cursor3 {                    // one K-half plane of the persistent K-tile stream
     int local;                      // walk position of the output tile it is in
@@ -90,9 +104,9 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
 
     // ---- producer side ----------------------------------------------------------------------------------------------
     // plane p of a K tile = 16 X pieces + 20 W pieces of 16 rows x 64 B; wave w issues X pieces w, w + 8, W pieces w, w + 8
-    // and, when p == grp, W piece 16 + (w & 3).  Lane l of a piece: row l / 4, slot l % 4 <- source chunk slot ^ ((row >> 2) & 3)
-    // = slot ^ ((l >> 4) & 3) (piece rows start at multiples of 16)
-    auto swz_bytes = [&](int l, int p) __attribute__((always_inline)) { return (((l & 3) ^ ((l >> 4) & 3)) * 16 + p * RBH); };
+    // and, when p == grp, W piece 16 + (w & 3).  Lane l of a piece: row l / 4, slot l % 4 <- source chunk
+    // slot ^ slot_swz((row >> 2) & 3) = slot ^ slot_swz((l >> 4) & 3) (piece rows start at multiples of 16)
+    auto swz_bytes = [&](int l, int p) __attribute__((always_inline)) { return (((l & 3) ^ slot_swz((l >> 4) & 3)) * 16 + p * RBH); };
     const TapGeo tg(a);
     // W pieces w + 8 and 16 + (w & 3) start 128 and 256 + 16 (w & 3) - 16 w rows after piece w (uniform byte distances)
     const unsigned wd1 = 128u * (unsigned)(Ktot * 2), wd2 = (unsigned)(256 + 16 * (wave & 3) - 16 * wave) * (unsigned)(Ktot * 2);
@@ -162,20 +176,22 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     };
 
     // ---- consumer side ----------------------------------------------------------------------------------------------
-    // fragment read addresses of ring slot 0, plane 0 (one register per 16-deep K step of a plane; accumulator tile and
-    // plane are immediates, the ring slot is added / subtracted per K tile)
-    // (the second 16-deep K step of a plane is the chunk with bit 1 flipped: address ^ 32)
+    // fragment read addresses of ring slot 0, plane 0 (fragment and plane are immediates, the ring slot is added / subtracted
+    // per K tile).  A plane is one 16x16x32 K step: lane l reads chunk l >> 4 of X row l & 15 of a 16-row fragment, and of the W
+    // row with bits 2 and 3 of l & 15 SWAPPED (16 v + 8 ((a >> 2) & 1) + 4 (a >> 3) + (a & 3) for A row a): with that row order
+    // the accumulators return to the 32x32 layout by lane-row swaps alone (see to_layout32 below)
     int xa, wa;
     {
-        const int sl = (lh ^ ((l31 >> 2) & 3)) * 16;
-        xa = (wm * MI3 * 32 + l31) * RBH + sl;
-        wa = XPL + (wn * NJ3 * 32 + l31) * RBH + sl;
+        const int r = lane & 15, c = lane >> 4;
+        const int rw = 8 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3);
+        xa = (wm * MI3 * 32 + r) * RBH + (c ^ slot_swz((r >> 2) & 3)) * 16;
+        wa = XPL + (wn * NJ3 * 32 + rw) * RBH + (c ^ slot_swz((rw >> 2) & 3)) * 16;
     }
 
     // The wave's 160 bias values travel through LDS one tile AHEAD: three 4-byte-per-lane LDS-DMA instructions issued at the
     // start of tile t bring tile t + 1's bias (columns beyond N read as zero through the descriptor's bounds check; no bias: an
     // empty descriptor, zeros arrive), landed long before tile t + 1 starts (every phase's counted wait covers them), so the
-    // accumulator initialisation is 20 LDS reads with no VMEM operation queued behind the previous epilogue's stores.  (The
+    // accumulator initialisation is 10 LDS reads with no VMEM operation queued behind the previous epilogue's stores.  (The
     // first version loaded the bias straight from global memory at tile start; tools/bias_probe.py shows no measurable
     // difference between the two, nor between bias and no bias -- its first reading, "bias costs 15 %", was the slower first
     // measurement after fresh allocations.)
@@ -207,17 +223,16 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     __builtin_amdgcn_s_barrier();
 
     f32x16 acc[MI3][NJ3];
-    f16x8 xf[MI3][2], wf[NJ3][2];
+    // The K loop runs on 16x16x32 MFMAs (the chip holds a higher clock on them than on 32x32x16 at the same matrix-pipe cycles:
+    // profiles/igemm320_k16_loop_bench.log).  The 16x16 tile with row half u and column half v of 32x32 block (I, J) lives in
+    // elements 4 (2 v + u) .. + 3 of acc[I][J]; its MFMA takes X fragment 2 I + u and W fragment 2 J + v.
+    f16x8 xf[2 * MI3], wf[2 * NJ3];
     auto phase = [&](auto pc, const int bo, const int bn) __attribute__((always_inline)) {
         constexpr int P = decltype(pc)::v;                         // K half
 #pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-            const int xk = k2 ? (xa ^ 32) : xa, wk = k2 ? (wa ^ 32) : wa;
+        for (int i = 0; i < 2 * MI3; ++i) xf[i] = *(const f16x8*)(smem + xa + P * PLANE + i * 16 * RBH);
 #pragma unroll
-            for (int i = 0; i < MI3; ++i) xf[i][k2] = *(const f16x8*)(smem + xk + P * PLANE + i * 32 * RBH);
-#pragma unroll
-            for (int j = 0; j < NJ3; ++j) wf[j][k2] = *(const f16x8*)(smem + wk + P * PLANE + j * 32 * RBH);
-        }
+        for (int j = 0; j < 2 * NJ3; ++j) wf[j] = *(const f16x8*)(smem + wa + P * PLANE + j * 16 * RBH);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (P == 0) { issue(cb, 1, bn); advance(cb, 1); }   // plane 1 of the next K tile
         else { issue(ca, 0, bo); advance(ca, 0); }                    // plane 0 of the K tile after it (this slot)
@@ -229,16 +244,57 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2)
+        for (int i = 0; i < MI3; ++i)
 #pragma unroll
-            for (int i = 0; i < MI3; ++i)
+            for (int j = 0; j < NJ3; ++j)
 #pragma unroll
-                for (int j = 0; j < NJ3; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[j][k2], xf[i][k2], acc[i][j], 0, 0, 0);
+                for (int q = 0; q < 4; ++q) {                      // q = 2 v + u
+                    f32x4 c = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[2 * j + (q >> 1)], xf[2 * i + (q & 1)], c, 0, 0, 0);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[i][j][4 * q + e] = c[e];
+                }
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
+    };
+
+    // ---- back to the 32x32 layout, once per tile / split-K item ---------------------------------------------------------------
+    // A 16x16x32 result has its column on l & 15 and row 4 (l >> 4) + r in register r.  With lane l = (c = l & 15, g0 = (l >> 4) & 1,
+    // g1 = l >> 5), A row a = 8 g1 + 4 g0 + r was loaded from W row 16 v + 8 g0 + 4 g1 + r (bits 2 and 3 swapped), so element
+    // 4 (2 v + u) + r of a block holds output row m = 16 u + c, column n = 16 v + 8 g0 + 4 g1 + r.  The 32x32 layout wants element
+    // 4 G + r of lane (c, bit 4 = u', bit 5 = h) to be m = 16 u' + c, n = 8 G + 4 h + r: h = g1 (lane bit 5 stays), G = 2 v + g0,
+    // u' = u.  Where u = g0 the value is in place; the others are element 8 v + r in the odd 16-lane rows (u = 0 held by g0 = 1,
+    // wanted at element 8 v + 4 + r of lane bit 4 = 0) and element 8 v + 4 + r in the even rows (u = 1 held by g0 = 0, wanted at
+    // element 8 v + r of lane bit 4 = 1): v_permlane16_swap_b32, which exchanges the odd rows of its first operand with the even
+    // rows of its second.  8 swaps per block, 80 per tile and wave, in place; afterwards register r of tile (i, j) is row
+    // 32 i + (l & 31), column 32 j + 8 (r >> 2) + 4 (l >> 5) + (r & 3), as every epilogue below expects.
+    auto to_layout32 = [&](f32x16 (&acc)[MI3][NJ3]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < MI3; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ3; ++j)
+#pragma unroll
+                for (int v = 0; v < 2; ++v)
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        // (scalar copies: __builtin_bit_cast applied to a vector ELEMENT reads element 0 of the vector)
+                        const float lo = acc[i][j][8 * v + s], hi = acc[i][j][8 * v + 4 + s];
+                        const auto sw = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi), false, false);
+                        const unsigned slo = sw[0], shi = sw[1];
+                        acc[i][j][8 * v + s] = __builtin_bit_cast(float, slo);
+                        acc[i][j][8 * v + 4 + s] = __builtin_bit_cast(float, shi);
+                    }
+    };
+
+    // (every block is ONE 16-register tuple at the points where this is called -- after the initial values, around the swaps --
+    // so that the register allocator keeps the 160 accumulators in place as ten tuples instead of 160 separately split values)
+    auto pin_tuples = [&](f32x16 (&acc)[MI3][NJ3]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < MI3; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ3; ++j) asm volatile("" : "+v"(acc[i][j]));
     };
 
     // ---- epilogue scratch: the ring plane that is FREE while an epilogue runs ---------------------------------------------
@@ -704,7 +760,8 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
         const int nw = tn * TBN3 + wn * NJ3 * 32;
         int idx_u = -1;                                            // >= 0: the one row-vector row of this wave's 64 rows
         if constexpr (RV) idx_u = rowvec_uniform_idx<32 * MI3>(a, mw);
-        // accumulators start at bias (from its LDS slot) + the wave's row of the row vector
+        // accumulators start at bias (from its LDS slot) + the wave's row of the row vector, in the K loop's layout: elements
+        // 8 v + 4 u .. + 3 of block (I, J) are columns 32 J + 16 v + 8 g0 + 4 g1 .. + 3 for both u and both I
         if (SPLIT && cph == 1) {
 #pragma unroll
             for (int i = 0; i < MI3; ++i)
@@ -714,21 +771,25 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
                     for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
         } else {
             const int lane_e = lane_now(lane);
-            const int lh_e = lane_e >> 5;
+            const int col_e = 8 * ((lane_e >> 4) & 1) + 4 * (lane_e >> 5);
 #pragma unroll
             for (int j = 0; j < NJ3; ++j)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 b = *(const f32x4*)(bias_lds + bslot * 768 + (32 * j + 8 * g + 4 * lh_e) * 4);
+                for (int v = 0; v < 2; ++v) {
+                    f32x4 b = *(const f32x4*)(bias_lds + bslot * 768 + (32 * j + 16 * v + col_e) * 4);
                     if (RV && idx_u >= 0) {
-                        int n = nw + 32 * j + 8 * g + 4 * lh_e;
+                        int n = nw + 32 * j + 16 * v + col_e;
                         n = n + 4 <= a.N ? n : 0;                   // columns beyond N are never stored
                         b += *(const f32x4*)(a.rowvec + (size_t)idx_u * a.N + n);
                     }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { acc[0][j][4 * g + e] = b[e]; acc[1][j][4 * g + e] = b[e]; }
+                    for (int e = 0; e < 4; ++e) {
+                        acc[0][j][8 * v + e] = b[e]; acc[0][j][8 * v + 4 + e] = b[e];
+                        acc[1][j][8 * v + e] = b[e]; acc[1][j][8 * v + 4 + e] = b[e];
+                    }
                 }
         }
+        pin_tuples(acc);
         if (grp == 1) __builtin_amdgcn_s_barrier();                // second wave group runs one barrier behind
         for (int kt = kb; kt < ke; ++kt, ++gt) {
             const int bo = (gt & 1) * SLOT, bn = SLOT - bo;        // ring slot of this K tile / of the next one
@@ -739,6 +800,9 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
             wa += d;
         }
         if (grp == 0) __builtin_amdgcn_s_barrier();                // both groups meet again: equal barrier counts per tile
+        pin_tuples(acc);
+        to_layout32(acc);
+        pin_tuples(acc);
 
         // ---- epilogue (no barriers; scratch = this wave's blocks of the free ring plane) --------------------------------
         char* eb = smem + ((gt - 1) & 1) * SLOT + PLANE + wave * 1024;

@@ -134,9 +134,25 @@ if __name__ == "__main__":
         print(f"fp32 slab swizzle {name:28s}: writes {w} (ideal {4 * 8}), reads {r} (ideal {4 * 4})")
 
 
-# ---- igemm320 (csrc/igemm320.hip): K-half planes with 64-byte rows, chunk c of row r in slot c ^ ((r >> 2) & 3) ------------
-def frag_read_320(k2):
-    return [(lane & 31) * 64 + (((k2 * 2 + (lane >> 5)) ^ (((lane & 31) >> 2) & 3)) * 16) for lane in range(64)]
+# ---- igemm320 (csrc/igemm320.hip): K-half planes with 64-byte rows, chunk c of row r in slot c ^ swz((r >> 2) & 3) ---------
+# 16x16x32 fragments: lane l reads chunk l >> 4 of row l & 15 (X) or of that row with bits 2 and 3 swapped (W).  swz = identity
+# (the swizzle of the former 32-row reads) is 2-way on them; swz(q) = q ^ ((q & 1) << 1) = {0, 3, 2, 1} is conflict-free for both
+def slot_swz(q):
+    return q ^ ((q & 1) << 1)
+
+
+def frag_read_320(k2, swz=slot_swz):      # the former 32x32x16 fragment read (two 16-deep K steps per plane)
+    return [(lane & 31) * 64 + (((k2 * 2 + (lane >> 5)) ^ swz(((lane & 31) >> 2) & 3)) * 16) for lane in range(64)]
+
+
+def frag_read_320_k16(w_rows, swz=slot_swz):
+    a = []
+    for lane in range(64):
+        r = lane & 15
+        if w_rows:
+            r = 8 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3)
+        a.append(r * 64 + (((lane >> 4) ^ swz((r >> 2) & 3)) * 16))
+    return a
 
 
 def h16b_off(r, c8):       # 32 rows x 32 fp16 columns (64-byte rows); 8-byte chunk c8 at c8 ^ ((r >> 1) & 7)
@@ -148,8 +164,11 @@ def f32h_off(r, c):        # 16 rows x 32 fp32 columns (128-byte rows)
 
 
 def igemm320_report():
+    for w_rows in (False, True):
+        report(f"igemm320 K loop 16x16x32 fragment read, {'W' if w_rows else 'X'} rows", "read_b128", frag_read_320_k16(w_rows))
+        report(f"  ... with the slot swizzle c ^ ((r >> 2) & 3)", "read_b128", frag_read_320_k16(w_rows, lambda q: q))
     for k2 in range(2):
-        report(f"igemm320 K loop fragment read, k2 = {k2}", "read_b128", frag_read_320(k2))
+        report(f"(32x32x16 fragment read on the same planes, k2 = {k2})", "read_b128", frag_read_320(k2))
     for g in range(4):
         report(f"igemm320 fp16 32x32 write g = {g}", "write_b64", [h16b_off(lane & 31, 2 * g + (lane >> 5)) for lane in range(64)])
     for p in range(2):
