@@ -115,6 +115,20 @@ enum { MOFA_TILE_AUTO = 0, MOFA_TILE_128X128 = 2, MOFA_TILE_192X128 = 4, MOFA_TI
 int mofa_igemm_f16(const mofa_igemm_args* a, mofa_stream_t stream);
 /* 1 when a launch with these arguments can emit `stats` (the value of a->stats itself is ignored), else 0 */
 int mofa_igemm_stats_ok(const mofa_igemm_args* a);
+/* What mofa_igemm_f16 would launch for `a` on a device of n_cu compute units, decided on the host alone (no device call; the
+ * pointers are looked at for NULL and alignment only).  All fields but rc are 0 when rc != MOFA_OK. */
+typedef struct mofa_igemm_plan_t {
+    int32_t rc;                        /* MOFA_OK, or the MOFA_EINVAL mofa_igemm_f16 returns without launching */
+    int32_t tile, kind;                /* the MOFA_TILE_* that runs; epilogue kind: bit 0 r1, bit 1 r2, bit 2 rowvec, 8 = GEGLU pair */
+    int32_t tiles_m, tiles_n, grid, threads, lds_bytes;
+    int32_t split;                     /* K slices of each remainder tile (1 = none) */
+    int32_t full_tiles, rem_tiles;     /* tiles computed whole / cut into `split` slices (split == 1: all tiles, 0) */
+    int32_t stats;                     /* the epilogue emits GroupNorm pair sums */
+    int32_t launches;                  /* 1, + 1 split-K fix-up, + 1 pair sums of the remainder tiles */
+    int32_t reserved[4];
+} mofa_igemm_plan_t;
+/* MOFA_EINVAL for a NULL a or out, or n_cu <= 0; else MOFA_OK with the launch's own verdict in out->rc */
+int mofa_igemm_plan(const mofa_igemm_args* a, int n_cu, mofa_igemm_plan_t* out);
 
 /* ------------------------------------------------------------------------------------------
  * Attention.  q/k/v are column blocks of token-major matrices: element (token, head, d) at

@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libmofa_hip.so")
 PROBE_LIB = os.path.join(HERE, "..", "tools", "libmofa_hip_probe.so")
 SOURCES = ["igemm.hip", "igemm8.hip", "igemm320.hip", "ff320.hip", "lin320.hip", "attention.hip", "norm.hip", "elementwise.hip", "softsplat.hip", "output.hip",
            "cmp_ops.hip", "frontend.hip", "landmarks.hip", "control.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "igemm_common.h"), os.path.join(CSRC, "igemm_pipe.h"),
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "igemm_common.h"), os.path.join(CSRC, "igemm_pipe.h"), os.path.join(CSRC, "igemm_plan.h"),
            os.path.join(CSRC, "landmarks_raster.h"), os.path.join(CSRC, "control_points.h"), os.path.join(HERE, "..", "include", "mofa_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 

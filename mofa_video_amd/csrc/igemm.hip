@@ -461,127 +461,38 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_f16_kernel(const mofa_i
 }
 
 extern "C" int mofa_igemm_f16(const mofa_igemm_args* a, mofa_stream_t stream) {
-    if (!a || !a->x || !a->w || !a->out) return MOFA_EINVAL;
-    if (a->M <= 0 || a->N <= 0 || a->Cin <= 0) return MOFA_EINVAL;
-    if (a->Cin % 64 != 0 || a->N % 4 != 0) return MOFA_EINVAL;
-    if (a->mode < 0 || a->mode > 2 || a->act < 0 || a->act > MOFA_ACT_GELU) return MOFA_EINVAL;
-    if (a->mode == MOFA_MODE_CONV3X3) {
-        if (a->Hin <= 0 || a->Win <= 0 || a->Hout <= 0 || a->Wout <= 0) return MOFA_EINVAL;
-        if ((a->stride != 1 && a->stride != 2) || (a->up != 1 && a->up != 2)) return MOFA_EINVAL;
-        if (a->ksize != 0 && a->ksize != 1 && a->ksize != 3 && a->ksize != 5 && a->ksize != 7) return MOFA_EINVAL;
-        if (a->dil < 0 || (a->dil > 1 && a->up != 1)) return MOFA_EINVAL;
-        if (a->pad != MOFA_PAD_SAME && a->pad != MOFA_PAD_TRAILING) return MOFA_EINVAL;
-        if (a->M % (a->Hout * a->Wout) != 0 || a->Hout > 65535 || a->Wout > 65535) return MOFA_EINVAL;
-    }
-    if (a->mode == MOFA_MODE_CONVT3 && (a->T < 0 || a->HW <= 0 || (a->T > 0 && a->M % (a->T * a->HW) != 0)))
-        return MOFA_EINVAL;
-    if (a->rowvec && (a->rv_div <= 0 || a->rv_mod_in <= 0 || a->rv_mod_out <= 0)) return MOFA_EINVAL;
-    if (a->act == MOFA_ACT_GEGLU_PAIR && (a->N % 64 != 0 || a->r1 || a->r2 || a->rowvec)) return MOFA_EINVAL;
-    if (a->ldx % 8 != 0 || a->ldo % 4 != 0) return MOFA_EINVAL;
-    if ((a->r1 && a->ldr1 % 4 != 0) || (a->r2 && a->ldr2 % 4 != 0)) return MOFA_EINVAL;
-
-    // two 4-wave configurations x nine epilogue kinds (bit 0 r1, bit 1 r2, bit 2 row vector; 8 = GEGLU pair); the third
-    // choice, the 8-wave phase-pipelined 256x256 tile, lives in igemm8.hip
-    struct Cfg { igemm_kern_t k[9]; int tm, tn, threads, lds, wg_per_cu; };
+    int rc = igemm_check_args(a);                             // refused before the device is touched
+    if (rc != MOFA_OK) return rc;
+    // two 4-wave configurations x nine epilogue kinds (bit 0 r1, bit 1 r2, bit 2 row vector; 8 = GEGLU pair); the 8-wave
+    // phase-pipelined 256x256 and 256x320 tiles live in igemm8.hip and igemm320.hip
 #define IGEMM_KINDS(WM, WN, MI)                                                                                        \
     {igemm_f16_kernel<WM, WN, MI, 0>, igemm_f16_kernel<WM, WN, MI, 1>, igemm_f16_kernel<WM, WN, MI, 2>,                \
      igemm_f16_kernel<WM, WN, MI, 3>, igemm_f16_kernel<WM, WN, MI, 4>, igemm_f16_kernel<WM, WN, MI, 5>,                \
      igemm_f16_kernel<WM, WN, MI, 6>, igemm_f16_kernel<WM, WN, MI, 7>, igemm_f16_kernel<WM, WN, MI, 8>}
-    static const Cfg cfgs[2] = {
-        {IGEMM_KINDS(2, 2, 2), 128, 128, 256, 2 * 256 * 128, 2},   // 128^2 tile, 2 workgroups per CU
-        {IGEMM_KINDS(2, 2, 3), 192, 128, 256, 2 * 320 * 128, 2},   // 192x128 tile: 2 x 80 KB = the whole LDS of a CU
-    };
-    if (a->tile != 0 && a->tile != MOFA_TILE_128X128 && a->tile != MOFA_TILE_192X128 && a->tile != MOFA_TILE_256X256 &&
-        a->tile != MOFA_TILE_256X320)
-        return MOFA_EINVAL;
-    if (a->stats && !igemm320_stats_ok(a)) return MOFA_EINVAL;   // GroupNorm pair sums from the epilogue: the 256x320 tile only
+    static const igemm_kern_t k128[9] = IGEMM_KINDS(2, 2, 2), k192[9] = IGEMM_KINDS(2, 2, 3);
     static LaunchSetup setup;                                 // LDS opt-in of every instantiation, CU count
-    int n_cu = setup.cus([](int) {
-        for (const Cfg& c : cfgs)
-            if (mofa_lds_optin(c.k, c.lds) != MOFA_OK) return MOFA_ELAUNCH;
-        return igemm8_init() == MOFA_OK && igemm320_init() == MOFA_OK ? MOFA_OK : MOFA_ELAUNCH;
+    const int n_cu = setup.cus([](int) {
+        return mofa_lds_optin(k128, igemm_tile(MOFA_TILE_128X128).lds) == MOFA_OK &&
+                       mofa_lds_optin(k192, igemm_tile(MOFA_TILE_192X128).lds) == MOFA_OK && igemm8_init() == MOFA_OK &&
+                       igemm320_init() == MOFA_OK
+                   ? MOFA_OK
+                   : MOFA_ELAUNCH;
     });
     if (n_cu == 0) return MOFA_ELAUNCH;
-    n_cu = n_cu >= 8 ? (n_cu / 8) * 8 : 8;                    // persistent grids are multiples of 8 (one per XCD): every tile /
-                                                              // round / split-K count below uses the SAME rounded figure
-    const int taps = igemm_taps(*a);
-    const long long Ktot = (long long)taps * a->Cin;
-    const int kind = a->act == MOFA_ACT_GEGLU_PAIR ? 8 : ((a->r1 ? 1 : 0) | (a->r2 ? 2 : 0) | (a->rowvec ? 4 : 0));
-    int choice = a->tile;                                     // MOFA_TILE_* or 0 = cost model
-    if (a->stats) choice = MOFA_TILE_256X320;
-    if (choice == 0) {
-        // Tile choice = the cheapest of  rounds of resident workgroups x CU time of one round, the latter modelled as
-        //   workgroups per CU x tile area x relative K-loop cost per flop x (1 + epilogue / K loop),  epilogue in K tiles:
-        //     128x128   1.00   two workgroups per CU
-        //     192x128   0.86   two workgroups fill the CU's 160 KB of LDS exactly; 17 % less fill / LDS-read traffic per
-        //                      flop, 50 % more MFMA work per barrier
-        //     256x256   0.62   8 waves, phase-pipelined K loop (igemm8.hip; needs 16-byte aligned rows)
-        // fitted to tools/igemm_tiles_bench.py on the denoise step's shapes (profiles/r02_igemm_tiles.md).  Rounds count the
-        // padding waste of partial tiles and the idle slots of the last round (e.g. N = 320: 2 x 256 wastes 37 %, 3 x 128
-        // 17 %; M = 7200: 570 tiles of 128x128 need two rounds of 512 slots, 380 tiles of 192x128 one).
-        static const double rel[2] = {1.00, 0.86};
-        static const int ids[2] = {MOFA_TILE_128X128, MOFA_TILE_192X128};
-        // epilogue cost in K tiles per epilogue kind (index = kind): 4-wave tiles (their epilogue overlaps the co-resident
-        // workgroup's K loop) / the 8-wave tile
-        static const double epi4[9] = {2.0, 3.5, 4.0, 4.0, 3.5, 4.0, 4.5, 4.5, 4.0};
-        static const double epi8[9] = {2.2, 5.2, 5.2, 6.0, 5.6, 5.5, 5.5, 6.3, 2.4};   // ([4]: fitted to the N = 320 choice, not the 2.6 measured)
-        const double nk = (double)(Ktot / 64);
-        double best = 0;
-        for (int k = 0; k < 2; ++k) {
-            const long long t = (long long)cdiv(a->M, cfgs[k].tm) * cdiv(a->N, cfgs[k].tn);
-            const long long slots_k = (long long)n_cu * cfgs[k].wg_per_cu;
-            const double cost = (double)((t + slots_k - 1) / slots_k) * cfgs[k].tm * cfgs[k].tn * rel[k] * cfgs[k].wg_per_cu *
-                                (1.0 + epi4[kind] / nk);
-            if (choice == 0 || cost < best) { best = cost; choice = ids[k]; }
-        }
-        {
-            const long long t = (long long)cdiv(a->M, 256) * cdiv(a->N, 256);
-            const double cost = (double)((t + n_cu - 1) / n_cu) * 256 * 256 * 0.62 * (1.0 + epi8[kind] / nk);
-            if (cost < best) { best = cost; choice = MOFA_TILE_256X256; }
-        }
-        if (kind != 7) {
-            // 256x320 (igemm320.hip): 0.58 per area (10 % less LDS-DMA, 7 % fewer fragment reads per flop than 256x256); its
-            // epilogues move 25 % more outputs per tile
-            static const double epi320[9] = {3.0, 7.5, 8.5, 9.5, 3.5, 7.9, 9.0, 12.0, 5.0};   // fitted: profiles/archive/r03_igemm_tiles_bench.log; r04: the
-            // residual kinds [1] [2] [3] [5] [6] lowered by 1.5-2 with the fp16-transposed residual epilogue (profiles/r04_res16_tiles_ab.log);
-            // [1], [5] lowered from 10.0 / 10.5 in r03c so that the K = N = 320 residual launches leave the 192x128 tile (alone a
-            // draw: 352-414 against 372-403 TF/s by box; in the clip - 0.27 %, profiles/archive/r03c_cost_model_and_splitk_ab.log:
-            // beside a second stream the 17 % of padded columns of 3 x 128 are no longer free)
-            const long long t = (long long)cdiv(a->M, 256) * cdiv(a->N, 320);
-            // a partial last round split along K (igemm320_split) costs 1 / S of a round + the fix-up pass
-            const int S = kind == 8 ? 1 : igemm320_split(t, (int)nk, n_cu, a->workspace ? a->workspace_bytes : 0);
-            const double rounds = S > 1 ? (double)(t / n_cu) + 1.0 / S + 0.12 : (double)((t + n_cu - 1) / n_cu);
-            // wide outputs (many column tiles: every CU of an XCD streams its own weight tile through the fabric) run
-            // relatively slower on this tile than on 256x256 (profiles/archive/r03_igemm_tiles_bench_geglu320.log: N = 3840 / 10240
-            // 7 / 15 % behind): +2 % per column tile beyond 6, at most +25 %
-            const int tn320 = cdiv(a->N, 320);
-            const double wide = 1.0 + (tn320 > 6 ? (tn320 - 6 > 12 ? 0.25 : 0.02 * (tn320 - 6)) : 0.0);
-            const double cost = rounds * 256 * 320 * 0.58 * wide * (1.0 + epi320[kind] / nk);
-            if (cost < best) { best = cost; choice = MOFA_TILE_256X320; }
-        }
-    }
-    if (choice == MOFA_TILE_256X320) {
-        const int rc = igemm320_launch(a, kind, n_cu, (hipStream_t)stream);
-        if (rc <= 0) return rc;                               // launched (0) or failed (< 0)
-        if (a->tile == MOFA_TILE_256X320 || a->stats) return MOFA_EINVAL; // explicitly requested but not eligible
-        choice = MOFA_TILE_256X256;                           // chosen by the model but not eligible: next best pipeline tile
-    }
-    if (choice == MOFA_TILE_256X256) {
-        const int rc = igemm8_launch(a, kind, n_cu, (hipStream_t)stream);
-        if (rc <= 0) return rc;                               // launched (0) or failed (< 0)
-        if (a->tile == MOFA_TILE_256X256) return MOFA_EINVAL; // explicitly requested but not eligible (alignment)
-        choice = MOFA_TILE_192X128;                           // chosen by the model but not eligible: fall back
-    }
-    const Cfg* sel = &cfgs[choice == MOFA_TILE_128X128 ? 0 : 1];
-    const Cfg& c = *sel;
-    const int tilesM = cdiv(a->M, c.tm), tilesN = cdiv(a->N, c.tn);
-    const long long nt = (long long)tilesM * tilesN;
-    if (nt > 0x7fffffffLL) return MOFA_EINVAL;
-    const int slots = n_cu * c.wg_per_cu;                     // resident workgroups (a multiple of 8 on gfx950)
-    const int grid = igemm_grid(nt, slots);
-    hipLaunchKernelGGL(c.k[kind], dim3(grid), dim3(c.threads), c.lds, (hipStream_t)stream, *a, tilesN, (int)nt);
+    const IgemmPlan plan = igemm_plan_checked(a, n_cu);
+    if (plan.rc != MOFA_OK) return plan.rc;
+    if (plan.tile == MOFA_TILE_256X320) return igemm320_launch(a, plan, (hipStream_t)stream);
+    if (plan.tile == MOFA_TILE_256X256) return igemm8_launch(a, plan, (hipStream_t)stream);
+    hipLaunchKernelGGL((plan.tile == MOFA_TILE_128X128 ? k128 : k192)[plan.kind], dim3(plan.grid), dim3(plan.threads), plan.lds_bytes,
+                       (hipStream_t)stream, *a, plan.tiles_n, plan.full_tiles);
     MOFA_CHECK_LAUNCH();
     return MOFA_OK;
 }
 
 extern "C" int mofa_igemm_stats_ok(const mofa_igemm_args* a) { return igemm320_stats_ok(a) ? 1 : 0; }
+
+extern "C" int mofa_igemm_plan(const mofa_igemm_args* a, int n_cu, mofa_igemm_plan_t* out) {
+    if (!a || !out || n_cu <= 0) return MOFA_EINVAL;
+    *out = igemm_plan(a, n_cu);
+    return MOFA_OK;
+}

@@ -932,7 +932,7 @@ __global__ __launch_bounds__(192) void igemm320_tile_stats_kernel(const f16* __r
 }  // namespace
 
 // (kind 7 = row vector + two residuals does not fit the register file beside 160 accumulators and occurs nowhere in the
-// model graph: it runs on the 4-wave tiles)
+// model graph: it runs on the 4-wave tiles, igemm320_eligible in igemm_plan.h)
 static const igemm320_kern_t k_igemm320[9] = {igemm320_f16_kernel<0>, igemm320_f16_kernel<1>, igemm320_f16_kernel<2>,
                                                igemm320_f16_kernel<3>, igemm320_f16_kernel<4>, igemm320_f16_kernel<5>,
                                                igemm320_f16_kernel<6>, nullptr, igemm320_f16_kernel<8>};
@@ -954,84 +954,28 @@ int igemm320_init() {
                : MOFA_ELAUNCH;
 }
 
-// can the 256x320 tile run these arguments?  (kind 7 has no kernel here)
-static bool igemm320_eligible(const mofa_igemm_args* a, int kind, int taps) {
-    if (kind == 7 || !igemm_pipe_eligible(a, kind, (long long)taps * a->Cin)) return false;
-    return (long long)(a->N + TBN3) * taps * a->Cin * 2 < 0x7ff00000LL;   // unclamped W row offsets stay below W_DEAD
-}
-
-// can a launch with these arguments emit mofa_igemm_args.stats?  (a->stats itself is not looked at)
-bool igemm320_stats_ok(const mofa_igemm_args* a) {
-    if (!a || !a->x || !a->w || !a->out || a->M <= 0 || a->N <= 0 || a->Cin <= 0 || a->Cin % 64 != 0) return false;
-    if (a->act != MOFA_ACT_NONE || a->r2 || (a->r1 && a->s1 != 1.0f)) return false;
-    if (a->M % 64 != 0 || a->N % TBN3 != 0) return false;
-    if (a->rowvec && (a->rv_mod_in != 1 || a->rv_div <= 0 || a->rv_div % 64 != 0)) return false;   // constant over a wave's 64 rows
-    if (a->tile != 0 && a->tile != MOFA_TILE_256X320) return false;
-    return igemm320_eligible(a, (a->r1 ? 1 : 0) | (a->rowvec ? 4 : 0), igemm_taps(*a));
-}
-
-// Split-K for the tiles of a partial last round.  T tiles on n_cu persistent workgroups take ceil(T / n_cu) tile times although
-// the last round may hold only a few tiles (M = 460800, N = 320: 1800 tiles = 7 rounds + 8 tiles; M = 7200: 116 tiles on 256
-// CUs).  When a workspace is supplied, the R = T mod n_cu remainder tiles are cut into S K-slices (R * S <= n_cu work items of
-// nk / S K tiles each, fp32 partial tiles in the workspace) and a small fix-up kernel adds the slices in slice order and
-// applies the epilogue: the round shrinks to about 1 / S of a tile time.  Returns S (1 = no split).
-int igemm320_split(long long T, int nk, int n_cu, long long ws_bytes) {
-    const long long R = T % n_cu;
-    if (ws_bytes <= 0 || R == 0) return 1;
-    if (T > n_cu && R * 10 > (long long)n_cu * 6) return 1;   // a last round that is more than 60 % full stays whole
-    long long s = n_cu / R;
-    if (s > 8) s = 8;
-    if (s > nk / 8) s = nk / 8;                                // at least eight K tiles per slice, and ... (r04: up to 16 slices
-                                                               // of >= 4 K tiles changes nothing on the per-rank shapes of an
-                                                               // 8-GPU run: mix 691 against 693 TF/s, profiles/r04_shard_shapes_tiles.log)
-    // ... only where it pays: a slice saves (1 - 1 / S) of a tile's K loop (about 2 us per K tile) but costs the partial-tile
-    // dump and the fix-up launch (about 25 us; profiles/archive/r03b_kernel_stats_bench.md: splitting the shallow-K launches of the
-    // clip -- 5 100 of 12 012 -- made it 4 % SLOWER)
-    if (s >= 2 && 2.0 * nk * (1.0 - 1.0 / (double)s) < 50.0) s = 1;
-    const long long per = (long long)TBM3 * TBN3 * 4;
-    while (s >= 2 && R * s * per > ws_bytes) --s;
-    return s >= 2 ? (int)s : 1;
-}
-
-// returns 0 launched, < 0 error, 1 not eligible (the caller falls back to another tile)
-int igemm320_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t stream) {
-    const int taps = igemm_taps(*a);
-    if (!igemm320_eligible(a, kind, taps)) return 1;
-    constexpr int tbn = TBN3;
-    const int tilesM = cdiv(a->M, TBM3), tilesN = cdiv(a->N, tbn);
-    const long long nt = (long long)tilesM * tilesN;
-    if (nt > 0x7fffffffLL) return MOFA_EINVAL;
-    Aux aux = igemm_pipe_aux(a, taps, tilesN);
-    const int nk = taps * (a->Cin / 64);
-    const bool ws_ok = a->workspace && (((size_t)a->workspace) & 15) == 0;
-    const int S = kind == 8 ? 1 : igemm320_split(nt, nk, n_cu, ws_ok ? a->workspace_bytes : 0);   // (the fix-up has no GEGLU form)
-    if (a->stats && (kind > 6 || !k_igemm320_stats[kind] || (((size_t)a->stats) & 15) || !igemm320_stats_ok(a))) return MOFA_EINVAL;
-    if (S == 1) {
-        hipLaunchKernelGGL(a->stats ? k_igemm320_stats[kind] : k_igemm320[kind], dim3(igemm_grid(nt, n_cu)), dim3(512), LDS_BYTES3, stream, *a, tilesN,
-                           (int)nt, aux);
-        MOFA_CHECK_LAUNCH();
-        return MOFA_OK;
+// One launch, or with plan.split > 1 (igemm320_split, igemm_plan.h): the whole tiles of the full rounds, then one K slice of a
+// remainder tile per workgroup; then the fix-up, and with stats the remainder tiles' pair sums from their finished outputs
+static_assert(TBM3 == 256 && TBN3 == 320 && LDS_BYTES3 == 159744, "igemm_plan.h's MOFA_TILE_256X320 row");
+int igemm320_launch(const mofa_igemm_args* a, const IgemmPlan& plan, hipStream_t stream) {
+    const int kind = plan.kind, S = plan.split, R = plan.rem_tiles, tilesN = plan.tiles_n;
+    Aux aux = igemm_pipe_aux(a, igemm_taps(*a), tilesN);
+    igemm320_kern_t kern = a->stats ? k_igemm320_stats[kind] : k_igemm320[kind];
+    if (S > 1) {
+        kern = a->stats ? k_igemm320_split_stats[kind] : k_igemm320_split[kind];
+        aux.nsplit = S, aux.nsplit_d = fastdiv_make(S);
+        aux.tile0 = plan.full_tiles, aux.nitems = R * S, aux.ws = (float*)a->workspace;
     }
-    // one launch: the whole tiles of the full rounds, then one K slice of a remainder tile per workgroup; then the fix-up
-    const long long full = nt - nt % n_cu;
-    const int R = (int)(nt - full), items = R * S;
-    aux.nsplit = S;
-    aux.nsplit_d = fastdiv_make(S);
-    aux.tile0 = (int)full;
-    aux.nitems = items;
-    aux.ws = (float*)a->workspace;
-    int grid = full > 0 ? (n_cu / 8) * 8 : ((items + 7) / 8) * 8;
-    if (grid < items) return MOFA_EINVAL;                       // (R * S <= n_cu by construction)
-    hipLaunchKernelGGL(a->stats ? k_igemm320_split_stats[kind] : k_igemm320_split[kind], dim3(grid), dim3(512), LDS_BYTES3, stream, *a,
-                       tilesN, (int)full, aux);
+    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.threads), plan.lds_bytes, stream, *a, tilesN, plan.full_tiles, aux);
     MOFA_CHECK_LAUNCH();
-    const long long pieces = (long long)R * TBM3 * (tbn / 8);
+    if (S == 1) return MOFA_OK;
+    const long long pieces = (long long)R * TBM3 * (TBN3 / 8);
     hipLaunchKernelGGL(igemm320_fixup_kernel, dim3((int)((pieces + 255) / 256)), dim3(256), 0, stream, *a,
-                       (const float*)a->workspace, (int)full, S, tilesN, R);
+                       (const float*)a->workspace, plan.full_tiles, S, tilesN, R);
     MOFA_CHECK_LAUNCH();
-    if (a->stats) {                                              // the remainder tiles' pair sums, from their finished outputs
+    if (a->stats) {
         hipLaunchKernelGGL(igemm320_tile_stats_kernel, dim3(R * 4), dim3(192), 0, stream, (const f16*)a->out, a->ldo, a->stats, a->M,
-                           a->N, (int)full, tilesN);
+                           a->N, plan.full_tiles, tilesN);
         MOFA_CHECK_LAUNCH();
     }
     return MOFA_OK;

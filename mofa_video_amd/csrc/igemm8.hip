@@ -571,13 +571,10 @@ int igemm8_init() {
     return MOFA_OK;
 }
 
-int igemm8_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t stream) {
-    const int taps = igemm_taps(*a);
-    if (!igemm_pipe_eligible(a, kind, (long long)taps * a->Cin)) return 1;   // the caller falls back to a 4-wave tile
-    const int tilesM = cdiv(a->M, TBM), tilesN = cdiv(a->N, TBN);
-    const long long nt = (long long)tilesM * tilesN;
-    if (nt > 0x7fffffffLL) return MOFA_EINVAL;
-    Aux aux = igemm_pipe_aux(a, taps, tilesN);
+int igemm8_launch(const mofa_igemm_args* a, const IgemmPlan& plan, hipStream_t stream) {
+    static_assert(TBM == 256 && TBN == 256 && LDS_BYTES == 163840, "igemm_plan.h's MOFA_TILE_256X256 row");
+    const int kind = plan.kind;
+    Aux aux = igemm_pipe_aux(a, igemm_taps(*a), plan.tiles_n);
     igemm8_kern_t kern = k_igemm8[kind];
 #ifdef MOFA_PROBE
     aux.trace = s_probe_trace;
@@ -586,7 +583,7 @@ int igemm8_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t stre
             if (k_probe_vars[i] == s_probe_var) kern = k_probe_kern[i];
     if (s_probe_var == 64 && k_trace_kern[kind]) kern = k_trace_kern[kind];
 #endif
-    hipLaunchKernelGGL(kern, dim3(igemm_grid(nt, n_cu)), dim3(512), LDS_BYTES, stream, *a, tilesN, (int)nt, aux);
+    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.threads), plan.lds_bytes, stream, *a, plan.tiles_n, plan.full_tiles, aux);
     MOFA_CHECK_LAUNCH();
     return MOFA_OK;
 }

@@ -1,9 +1,11 @@
 // Pieces shared by the three implicit-GEMM translation units (igemm.hip: 4-wave tiles + the launcher; igemm8.hip and
-// igemm320.hip: the 8-wave phase-pipelined 256x256 and 256x320 kernels, which share more in igemm_pipe.h): the tap count,
-// the XCD-aware persistent tile walk and its grid size, the epilogue kind bits, the counted waits and the 8-wave launchers'
-// prototypes; for the 4-wave kernels also the two-register row geometry, its tap source and the pointer LDS-DMA primitive.
+// igemm320.hip: the 8-wave phase-pipelined 256x256 and 256x320 kernels, which share more in igemm_pipe.h):
+// the XCD-aware persistent tile walk, the epilogue kind bits, the counted waits and the 8-wave launchers' prototypes; for the
+// 4-wave kernels also the two-register row geometry, its tap source and the pointer LDS-DMA primitive.  Every host-side
+// decision (tile, grid, split-K) is igemm_plan.h's.
 #pragma once
 #include "common.h"
+#include "igemm_plan.h"
 
 struct RowGeo {   // two registers per DMA row group
     int a;        // plain / convT3: global output row m; conv: image index; -1 when the row is beyond M
@@ -59,10 +61,6 @@ __device__ __forceinline__ const f16* x_src(const mofa_igemm_args& a, const RowG
     }
 }
 
-__host__ __device__ __forceinline__ int igemm_taps(const mofa_igemm_args& a) {
-    return (a.mode == MOFA_MODE_CONV3X3) ? (a.ksize > 0 ? a.ksize * a.ksize : 9) : (a.mode == MOFA_MODE_CONVT3 ? 3 : 1);
-}
-
 // XCD-aware persistent tile walk: the hardware deals workgroup ids round-robin over the 8 XCDs, so workgroup b lives on
 // XCD b & 7.  Each XCD gets a CONTIGUOUS range of tile ids (bijective split of ntiles into 8 ranges) and its resident
 // workgroups walk that range with stride (workgroups per XCD): at any time one XCD works on neighbouring tiles (same
@@ -77,11 +75,7 @@ struct TileWalk {
         stride = gridDim.x >> 3;
     }
 };
-// its grid: one workgroup per tile up to `slots` resident workgroups, a multiple of 8 (equal shares per XCD), at least 8
-static inline int igemm_grid(long long ntiles, int slots) {
-    const int grid = (int)(ntiles < slots ? ((ntiles + 7) / 8) * 8 : (slots / 8) * 8);
-    return grid < 8 ? 8 : grid;
-}
+// (its grid: igemm_grid, igemm_plan.h)
 
 #define EPI_R1 1
 #define EPI_R2 2
@@ -104,12 +98,9 @@ __device__ __forceinline__ void wait_vmcnt_only() {
 }
 __device__ __forceinline__ void wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// host side: igemm8.hip's launcher, called by mofa_igemm_f16 when the 8-wave tile is chosen / forced
+// host side: the 8-wave launchers run what mofa_igemm_f16's plan says (plan.tile is theirs): MOFA_OK or MOFA_ELAUNCH
 typedef void (*igemm_kern_t)(const mofa_igemm_args, const int, const int);
-int igemm8_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t stream);
+int igemm8_launch(const mofa_igemm_args* a, const IgemmPlan& plan, hipStream_t stream);
 int igemm8_init();
-// igemm320.hip: the 256x320 tile (same return convention: 0 launched, < 0 error, 1 not eligible)
-int igemm320_launch(const mofa_igemm_args* a, int kind, int n_cu, hipStream_t stream);
+int igemm320_launch(const mofa_igemm_args* a, const IgemmPlan& plan, hipStream_t stream);
 int igemm320_init();
-bool igemm320_stats_ok(const mofa_igemm_args* a);             // mofa_igemm_args.stats can be emitted for these arguments
-int igemm320_split(long long tiles, int nk, int n_cu, long long ws_bytes);   // K slices for the remainder tiles (1 = none)

@@ -3,7 +3,7 @@
 // geometry of a DMA row group and its tap source, the buffer-descriptor LDS-DMA wrapper, the cursors' tap advance, the
 // wave-uniform row-vector index, the activation and the epilogue's scratch images (32 x 64 fp16 with its row read-back, 32 x 32
 // fp32).
-// Host side: fastdiv_make, the eligibility test both launchers share and the set-up of Aux.
+// Host side: fastdiv_make and the set-up of Aux (eligibility: igemm_plan.h).
 #pragma once
 #include "igemm_common.h"
 
@@ -182,35 +182,6 @@ static inline FastDiv fastdiv_make(int d) {
     }
     return f;
 }
-
-// rows of the activation buffer the launch may address (convT3 without clipping: one halo frame on either side)
-static inline long long igemm8_rows_in(const mofa_igemm_args* a) {
-    if (a->mode == MOFA_MODE_CONV3X3) return a->M / ((long long)a->Hout * a->Wout) * a->Hin * a->Win;
-    if (a->mode == MOFA_MODE_CONVT3 && a->T == 0) return (long long)a->M + 2ll * a->HW;
-    return a->M;
-}
-
-
-// 16-byte row alignment everywhere (the kernel has no narrow-store path); packed row geometry and 32-bit offsets in range
-static inline bool igemm_pipe_eligible(const mofa_igemm_args* a, int kind, long long Ktot) {
-    const int nout = kind == 8 ? a->N / 2 : a->N;
-    if ((a->ldo & 7) || (nout & 7) || (a->N & 7) || (((size_t)a->out) & 15) || (((size_t)a->x) & 15)) return false;
-    if (a->r1 && ((a->ldr1 & 7) || (((size_t)a->r1) & 15))) return false;
-    if (a->r2 && ((a->ldr2 & 7) || (((size_t)a->r2) & 15))) return false;
-    if (a->bias && (((size_t)a->bias) & 15)) return false;
-    if ((a->r1 || a->r2 || a->rowvec) && a->act != MOFA_ACT_NONE) return false;   // only the plain kind carries activation code here
-    if (a->rowvec && (((size_t)a->rowvec) & 15)) return false;
-    if ((long long)a->N * Ktot * 2 >= (1ll << 32) || (((size_t)a->w) & 15)) return false;
-    if (a->mode == MOFA_MODE_CONV3X3) {
-        const long long nimg = a->M / ((long long)a->Hout * a->Wout);
-        if (a->Hout > 1024 || a->Wout > 1024 || nimg > 2047) return false;
-    } else if (a->mode == MOFA_MODE_CONVT3) {
-        if (a->M >= (1 << 29)) return false;
-    }
-    if (igemm8_rows_in(a) * a->ldx * 2 >= (1ll << 32) - 65536) return false;   // 32-bit buffer offsets
-    return true;
-}
-
 
 // launch-invariant scalars of a launch (tilesN = output tile columns of the chosen tile)
 static inline Aux igemm_pipe_aux(const mofa_igemm_args* a, int taps, int tilesN) {

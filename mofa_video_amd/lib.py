@@ -40,6 +40,11 @@ class IgemmArgs(C.Structure):
     ]
 
 
+class IgemmPlan(C.Structure):                       # mofa_igemm_plan_t
+    _fields_ = [(n, C.c_int32) for n in ("rc", "tile", "kind", "tiles_m", "tiles_n", "grid", "threads", "lds_bytes", "split",
+                                         "full_tiles", "rem_tiles", "stats", "launches")] + [("reserved", C.c_int32 * 4)]
+
+
 class Ff320Args(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("pos", C.c_void_p), ("w1p", C.c_void_p), ("b1", C.c_void_p), ("w2p", C.c_void_p), ("b2", C.c_void_p),
@@ -87,6 +92,7 @@ PROTOTYPES = {
     "mofa_version": [],
     "mofa_igemm_f16": [_P, _P],                     # (const mofa_igemm_args*: a byref(IgemmArgs) or the packed 192 bytes)
     "mofa_igemm_stats_ok": [_P],
+    "mofa_igemm_plan": [_P, _I, _P],                # (const mofa_igemm_args*, n_cu, mofa_igemm_plan_t*: a byref(IgemmPlan)); no device call
     "mofa_ff320_f16": [_P, _P],
     "mofa_lin320_f16": [_P, _P],                    # (const mofa_lin320_args*: the packed 112 bytes)                     # (const mofa_ff320_args*: the packed 152 bytes)
     "mofa_attn_spatial_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],

@@ -24,7 +24,10 @@ Two input families:
 
 Three epilogues: ``bias``, ``relu`` (bias + ReLU, the CMP encoder's form) and ``r1`` (bias, then the residual with s1 = 1:
 round16(round16(acc + bias) + r1), the formula of test_igemm_tiles_gpu.py::test_all_tiles_round_residual_adds_alike)."""
+import ctypes
 import functools
+import os
+import sys
 import types
 
 import torch
@@ -32,6 +35,9 @@ import torch
 import op_cases as oc
 from op_cases import F16, NAN, TOL, Case, close_errors, guard, run  # noqa: F401  (re-exported for the two test files)
 from mofa_video_amd import lib as L
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
+import igemm_plan_table as plan_table  # noqa: E402  (the rows of tests/igemm_plan_table.json and their mofa_igemm_args)
 
 EPIS = ("bias", "relu", "r1")
 FAMILIES = ("E", "A")
@@ -130,7 +136,7 @@ CONV_BY_ID = {s.id: s for s in CONV_ROWS}
 WAVE4_ONLY = ("k3-H40000",)                                  # Hout > 1024: the 8-wave tiles refuse, the default falls back
 
 # split-K on the 256x320 tile with a K slice that starts inside a tap of a k != 3 / dilated conv: two remainder tiles (M in
-# 257 ... 512, N = 320) cut into SPLIT_SLICES[id] slices for any CU count >= 16 (split_slices re-derives igemm320_split)
+# 257 ... 512, N = 320) cut into SPLIT_SLICES[id] slices for any CU count >= 16 (assert_table asks mofa_igemm_plan)
 SPLIT_ROWS = [
     conv("split-k5-c128", 11, 13, k=5, Cin=128, N=320, M=286),
     conv("split-k5d2-c128", 11, 13, k=5, dil=2, Cin=128, N=320, M=286),
@@ -186,6 +192,18 @@ def plain_epi(s):
     return EPIS[(PLAIN_K.index(s.Cin) + PLAIN_M.index(s.M) + PLAIN_N.index(s.N)) % 3]
 
 
+def plan(s, epi="bias", tile=None, n_cu=256, split_k=True):
+    """mofa_igemm_plan (csrc/igemm_plan.h, no device call) for the launch ``case(s, "E", epi, tile, split_k)`` makes: the case's
+    leading dimensions, fake 16-byte aligned addresses (the guarded views are aligned alike) -> lib.IgemmPlan"""
+    mode = {"plain": L.MODE_PLAIN, "conv": L.MODE_CONV3X3, "convt": L.MODE_CONVT3}[s.mode]
+    a = plan_table.make_args(s.M, s.N, s.Cin, 1 if "r1" in epi else 0, mode, None if s.mode == "plain" else s.geom,
+                             L.ACT_RELU if "relu" in epi else None, split_k is not False, False, TILES[tile] if tile else L.TILE_AUTO,
+                             ldx=s.Cin + 24, ldo=(s.N + 39) // 8 * 8, ldr=(s.N + 55) // 8 * 8)
+    p = L.IgemmPlan()
+    assert L.load().mofa_igemm_plan(ctypes.byref(a), n_cu, ctypes.byref(p)) == 0
+    return p
+
+
 def assert_table():
     """the tables hold what they are there for: every kernel size and dilation, both strides, both ``up``, both pads, one and
     two K tiles per tap, more than one column tile for each tile width, each packing edge (and the shapes beyond them)"""
@@ -222,22 +240,10 @@ def assert_table():
         nk = s.taps * s.Cin // 64
         assert 256 < s.M <= 512 and s.N <= 320 and (s.k != 3 or s.dil != 1), s.id
         for n_cu in (16, 64, 256, 304):
-            assert split_slices(2, nk, n_cu // 8 * 8) == SPLIT_SLICES[s.id], (s.id, n_cu)
+            p = plan(s, tile="256x320", n_cu=n_cu)
+            assert (p.rc, p.tile, p.rem_tiles, p.split) == (0, L.TILE_256X320, 2, SPLIT_SLICES[s.id]), (s.id, n_cu, p.split)
         assert any((i * nk // SPLIT_SLICES[s.id]) % (s.Cin // 64) for i in range(1, SPLIT_SLICES[s.id])) or s.Cin == 64, s.id
         # ^ a slice starts in the middle of a tap wherever a tap has more than one K tile
-
-
-def split_slices(tiles, nk, n_cu, ws_bytes=256 * 256 * 320 * 4):
-    """igemm320_split (csrc/igemm320.hip) re-derived: K slices for the ``tiles % n_cu`` remainder tiles of a launch"""
-    R = tiles % n_cu
-    if ws_bytes <= 0 or R == 0 or (tiles > n_cu and R * 10 > n_cu * 6):
-        return 1
-    s = min(n_cu // R, 8, nk // 8)
-    if s >= 2 and 2.0 * nk * (1.0 - 1.0 / s) < 50.0:
-        s = 1
-    while s >= 2 and R * s * 256 * 320 * 4 > ws_bytes:
-        s -= 1
-    return s if s >= 2 else 1
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

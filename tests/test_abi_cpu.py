@@ -52,7 +52,8 @@ def test_every_entry_point_rejects_null_arguments_without_gpu():
     device call (there is no GPU in this container: a launch attempt would return MOFA_ELAUNCH or crash instead)"""
     from mofa_video_amd import lib
     l = lib.load()
-    query = {"mofa_version", "mofa_gn_nparts", "mofa_softsplat_ws_bytes", "mofa_flow_to_image_ws_bytes", "mofa_igemm_stats_ok"}
+    query = {"mofa_version", "mofa_gn_nparts", "mofa_softsplat_ws_bytes", "mofa_flow_to_image_ws_bytes", "mofa_igemm_stats_ok",
+             "mofa_igemm_plan"}
     checked = 0
     for name, argtypes in lib.PROTOTYPES.items():
         if name in query:

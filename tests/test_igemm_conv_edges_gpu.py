@@ -37,6 +37,14 @@ def _einval():
     return dict(expected_exception=MofaHipError, match=r"mofa_igemm_f16 failed with code -22$")
 
 
+def _plan(s, epi="bias", tile=None):
+    """what the launcher decides for this case on this device (mofa_igemm_plan)"""
+    return cc.plan(s, epi, tile, n_cu=torch.cuda.get_device_properties(0).multi_processor_count)
+
+
+WAVE4 = (cc.TILES["128x128"], cc.TILES["192x128"])
+
+
 def _launch(ops, s, family, epi, tile, fresh=False, split_k=None):
     """one launch, checked -> (its messages, the result on the device)"""
     c = cc.case(s, family, epi, tile, split_k)
@@ -62,6 +70,7 @@ def test_conv_matrix(ops, s, tile):
     if s.id in cc.WAVE4_ONLY and tile in cc.PIPE:            # Hout > 1024 does not fit the 10-bit field: refused, not truncated
         with pytest.raises(**_einval()):
             cc.run(ops, cc.case(s, "E", "bias", tile), DEV)
+        assert _plan(s, tile=tile).rc == -22
         return
     bad, worst = _matrix(ops, s, tile, cc.EPIS)
     print(f"CONV-EDGE {s.id} {tile}: family E {'equal' if not bad else 'DIFFERS'}, family A worst err / bound {worst:.3f}")
@@ -100,6 +109,7 @@ def test_refused_forced_tiles(ops, tile):
         if tile in cc.PIPE:
             with pytest.raises(**_einval()):
                 cc.run(ops, cc.case(s, "E", epi, tile), DEV)
+            assert _plan(s, epi, tile).rc == -22
         else:
             bad += _launch(ops, s, "E", epi, tile)[1]
     assert not bad, bad
@@ -108,12 +118,14 @@ def test_refused_forced_tiles(ops, tile):
 @pytest.mark.parametrize("s", cc.PIPE_OVER_ROWS, ids=repr)
 def test_packing_edges_of_the_8_wave_tiles(ops, s):
     """Wout = 1025 and 2048 images, one past the 10-bit ox field and the img << 20 field: the forced 8-wave tiles refuse, the
-    launcher's own choice (a 4-wave tile where the cost model asks for an 8-wave one) is exact"""
+    launcher's own choice is exact and, by its plan, a 4-wave tile (at N = 72 the model's first choice; with the fall-back from an
+    8-wave choice at N = 320: tests/test_igemm_plan_cpu.py)"""
     for tile in cc.PIPE:
         with pytest.raises(**_einval()):
             cc.run(ops, cc.case(s, "E", "bias", tile), DEV)
     bad, _ = _matrix(ops, s, None, cc.EPIS)
     assert not bad, (len(bad), bad[:6])
+    assert all(_plan(s, epi).tile in WAVE4 for epi in cc.EPIS)
 
 
 def test_wave4_oy_edge(ops):
@@ -125,6 +137,7 @@ def test_wave4_oy_edge(ops):
     s = cc.CONV_BY_ID["k3-H40000"]
     bad, _ = _matrix(ops, s, None, cc.EPIS)
     assert not bad, (len(bad), bad[:6])
+    assert all(_plan(s, epi).tile in WAVE4 for epi in cc.EPIS)
     for tile in (None,) + tuple(cc.TILES):
         with pytest.raises(**_einval()):
             cc.run(ops, cc.case(cc.WAVE4_OVER_ROW, "E", "bias", tile), DEV)
@@ -132,8 +145,8 @@ def test_wave4_oy_edge(ops):
 
 @pytest.mark.parametrize("s", cc.SPLIT_ROWS, ids=repr)
 def test_split_k_slice_starts_inside_a_tap(ops, s):
-    """the 256x320 tile cuts the two remainder tiles of these launches into 6 / 6 / 6 / 8 / 4 K slices (conv_cases.split_slices,
-    asserted in the CPU file for 16 CUs and more): cur_setup rebuilds (ky, kx, K tile within the tap) from a slice start in the
+    """the 256x320 tile cuts the two remainder tiles of these launches into 6 / 6 / 6 / 8 / 4 K slices (conv_cases.SPLIT_SLICES,
+    asserted against mofa_igemm_plan in the CPU file for 16 CUs and more): cur_setup rebuilds (ky, kx, K tile within the tap) from a slice start in the
     middle of a tap with ksize 5 / 7 (aux.ks_d) and with dilation.  Family E: split and whole launches equal each other and the
     reference.  Family A: both inside the tolerance, NOT equal (the proof that the split path ran: another fp32 summation
     order), and the split result bit-identical on a repeat launch"""

@@ -102,6 +102,11 @@ def test_plain_gemm_every_tile_every_kind(ops, tile, kind):
         from mofa_video_amd.lib import MofaHipError
         with pytest.raises(MofaHipError):
             ops.igemm(x, w, bias, tile=TILES[tile], **kw)
+        from conv_cases import plan_table               # the launcher's plan says the same, and where its own choice goes instead
+        from mofa_video_amd import lib
+        bits, cus = ("r1" in kind) | 2 * ("r2" in kind) | 4 * ("rv" in kind), torch.cuda.get_device_properties(0).multi_processor_count
+        forced, auto = (plan_table.plan(lib.load(), plan_table.make_args(M, N, K, bits, act=kw["act"], tile=t), cus) for t in (TILES[tile], 0))
+        assert forced[0] == -22 and auto[0] == 0 and auto[1] != TILES[tile] and (kind != "rvusilu" or auto[1] in (2, 4))
         return
     out = ops.igemm(x, w, bias, tile=TILES[tile], **kw)
     _close(out, apply(x.float() @ w.float().t()), what=f"plain {tile} {kind}")
