@@ -174,13 +174,24 @@ int mofa_attn_temporal_masked_f16(const void* q, const void* k, const void* v, v
  * of more than 32 frames (it accepts shorter ones too, and then agrees with mofa_attn_temporal_f16 up to fp32 summation
  * order).  Row layout of mofa_attn_temporal_f16 with Tq == T: q / k / v / out token row of (clip b, frame t, pixel p) =
  * (b*T + t)*HW + p, leading dims ld (q), ldkv (k and v), ldo (out), all multiples of 8.  No key mask and no Tq < T:
- * frame-sharded clips stay with the 32-key entry points above.  One wave per sequence keeps ceil(T/32) key tiles of K and
+ * frame-sharded clips take the 32-key entry points above or mofa_attn_temporal_long_masked_f16 below.  One wave per sequence keeps ceil(T/32) key tiles of K and
  * V in LDS (read from memory once) and the score tiles of one 32-query block in registers; rows of frames >= T are never
  * read or written.  MOFA_EINVAL for NULL pointers, T < 1 or T > 128, another head_dim, a leading dimension that is not a
  * positive multiple of 8, or a non-positive count -- all checked before any device call. */
 int mofa_attn_temporal_long_f16(const void* q, const void* k, const void* v, void* out,
                                 int nclips, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
                                 float scale, mofa_stream_t stream);
+/* The long temporal attention of a frame-sharded clip: Tq query frames (rows of q / out, clip stride Tq*HW) against
+ * 1 <= Tq <= T <= 128 key slots of the gathered K|V buffer (rows of k / v, clip stride T*HW).  key_mask: HOST memory, four
+ * 32-bit words read during the call, bit j % 32 of word j / 32 = key slot j exists; NULL = every slot below T; bits at or
+ * above T are ignored.  The words travel as kernel arguments (no device buffer, no extra launch).  A slot whose bit is clear
+ * is never read, neither K nor V (padding slots of uneven shards may hold NaN), and has weight exactly 0; query rows >= Tq
+ * are neither read nor written.  Every slot live and Tq == T: bit-identical with mofa_attn_temporal_long_f16.  MOFA_EINVAL
+ * for NULL tensor pointers, Tq < 1, Tq > T, T > 128, another head_dim, a leading dimension that is not a positive multiple
+ * of 8, a non-positive count, or a mask with no live slot below T -- all checked before any device call. */
+int mofa_attn_temporal_long_masked_f16(const void* q, const void* k, const void* v, void* out,
+                                       int nclips, int Tq, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
+                                       float scale, const uint32_t* key_mask, mofa_stream_t stream);
 /* in-place row softmax of an fp16 [rows][cols] matrix (VAE mid-block attention, 1 head x 512) */
 int mofa_softmax_rows_f16(void* x, int rows, int cols, int ld, mofa_stream_t stream);
 

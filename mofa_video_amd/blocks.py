@@ -457,7 +457,7 @@ class TransformerSpatioTemporal:
         fn = None
         if self.ff_in.can_fuse:
             f_own = None
-            if c.par is not None and c.par.kv_slots <= 32 and c.par.kv_inplace and c.par.gather_hidden:
+            if c.par is not None and c.par.kv_slots <= c.par.max_key_slots and c.par.kv_inplace and c.par.gather_hidden:
                 hid, f_own = c.par.kv_buffer(HW, self.C, h.device)            # norm1(f) straight into this shard's gather slot
             f, fn = self.ff_in.fused(h, pos=pos, HW=HW, T=T, ln_out=(self.tnorm1.g, self.tnorm1.b, f_own), ln_eps=self.tnorm1.eps)
         else:
@@ -470,7 +470,7 @@ class TransformerSpatioTemporal:
             # buffer, one all_gather_into_tensor (asynchronous, RCCL's stream) fills the other slots while the Q
             # projection runs, and the attention kernel masks the padding frames of the shorter shards.
             Cc, par = self.C, c.par
-            if par.kv_slots <= 32 and par.kv_inplace and par.gather_hidden:
+            if par.kv_slots <= par.max_key_slots and par.kv_inplace and par.gather_hidden:
                 # gather the NORMED HIDDEN tokens (C columns) instead of K|V (2C): half the bytes over xGMI; every rank then
                 # projects K|V for all key slots itself (4 x the rows of a 2C x C GEMM at 4 frame shards: ~0.1 ms at level 0
                 # against ~1 ms of transfer saved).  LayerNorm writes this shard's slot of the gather buffer in place; the
@@ -483,18 +483,18 @@ class TransformerSpatioTemporal:
                 q = self.tattn1.q(fn)
                 work.wait()
                 kv = ops.igemm(hid, self.tattn1.wqkv[Cc:])
-                a = ops.attn_temporal(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
-                                      head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
-            elif par.kv_slots <= 32 and par.kv_inplace:
+                a = ops.attn_temporal_sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
+                                              head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
+            elif par.kv_slots <= par.max_key_slots and par.kv_inplace:
                 fn = fn if fn is not None else self.tnorm1(f)
                 kv, own = par.kv_buffer(HW, 2 * Cc, fn.device)
                 self.tattn1.kv_into(fn, own)
                 work = par.kv_gather_begin(kv, HW)
                 q = self.tattn1.q(fn)
                 work.wait()
-                a = ops.attn_temporal(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
-                                      head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
-            else:   # more than 32 key slots after padding (e.g. 31 frames over 3 shards), or the in-place path failed
+                a = ops.attn_temporal_sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
+                                              head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
+            else:   # more than par.max_key_slots slots after padding (31 frames over 3 shards; 128 over 3 at a limit of 128), or the in-place path failed
                     # its self-check on this transport (parallel.FrameParallel.self_check): compact to T_full frames
                 fn = fn if fn is not None else self.tnorm1(f)
                 q, k, v = self.tattn1.qkv(fn)
@@ -502,8 +502,8 @@ class TransformerSpatioTemporal:
                 ops.copy2d(k, kv[:, :Cc])
                 ops.copy2d(v, kv[:, Cc:])
                 kv = par.gather_frames(kv, HW)
-                a = ops.attn_temporal(q, kv[:, :Cc], kv[:, Cc:], 1, par.T_full, HW, self.heads,
-                                      head_dim=self.tattn1.head_dim, Tq=T)
+                a = ops.attn_temporal_sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.T_full, HW, self.heads,
+                                              head_dim=self.tattn1.head_dim, Tq=T)
         # temporal cross-attention row vector.  diffusers 0.24.0 quirk: token row (b, s) of the GLOBAL batch takes the
         # context of batch (b*HW + s) mod B_global; v_tm has one row per global batch element.
         Bg = v_tm.shape[0]

@@ -747,18 +747,205 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_long_kernel(const f16*
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Long temporal attention of frame-sharded clips: attn_temporal_long_kernel with Tq <= T query frames (rows of q / out, clip
+// stride Tq*HW) against T <= 128 key slots of the gathered K|V buffer (rows of k / v, clip stride T*HW) under a 128-bit key
+// mask -- four wave-uniform kernel arguments m0 .. m3, bit j % 32 of word j / 32 = slot j exists; the host clears the bits at
+// and above T, so the kernel tests the mask alone.  The same fragment algebra, staging and LDS layout; a query's arithmetic
+// is that of the self-attention kernel (bit-identical with every slot live).  A dead slot is never read (neither K nor V: the
+// padding slots of the gathered buffer may hold NaN), its LDS rows are zero and its score is -1e30, tested in EVERY tile;
+// query rows >= Tq are neither loaded nor stored and the query loop runs ceil(Tq / 32) blocks.  A kernel of its own, not a
+// template flag on the one above: sharing the body moved that kernel's register allocation (D = 64: KT = 2 124 -> 126 VGPRs,
+// KT = 4 40 -> 50 AGPRs).
+// ---------------------------------------------------------------------------------------------------
+template <int D, int KT, int WPB>
+__global__ __launch_bounds__(64 * WPB) void attn_temporal_long_masked_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                             const f16* __restrict__ v, f16* __restrict__ out,
+                                                                             long long nseq, int Tq, int T, int HW, int heads,
+                                                                             int ld, int ldkv, int ldo, float scale, unsigned m0,
+                                                                             unsigned m1, unsigned m2, unsigned m3) {
+    constexpr int DC = D / 8;       // 16-byte chunks per row
+    constexpr int KK = D / 16;      // MFMA k-steps of S^T
+    constexpr int DB = D / 32;      // 32-wide output d-blocks
+    constexpr int KSTR = D + 8;     // K row stride in halves (conflict-free ds_read_b128)
+    constexpr int VSTR = D + 32;    // V row stride in halves (see lds_read_tr4)
+    constexpr int ROWS = 32 * KT;   // staged key rows
+    constexpr int RPI = 64 / DC;    // key rows one wave-wide pass of 16-byte chunks covers (8 / 4)
+    constexpr int UB = 4;           // passes in flight: 2 UB 16-byte loads per lane before the first LDS store
+    extern __shared__ __attribute__((aligned(16))) char smem_tl[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long seq = (long long)blockIdx.x * WPB + wave;
+    if (seq >= nseq) return;                                       // (no workgroup barrier below: LDS regions are per wave)
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int head = (int)(seq % heads);
+    const long long bp = seq / heads;
+    const int p = (int)(bp % HW);
+    const int b = (int)(bp / HW);
+    const size_t base = ((size_t)b * T * HW + p);                  // k / v token row of frame 0
+    const size_t qbase = ((size_t)b * Tq * HW + p);                // q / out token row of frame 0
+    f16* wK = (f16*)smem_tl + (size_t)wave * (ROWS * (KSTR + VSTR));
+    f16* wV = wK + ROWS * KSTR;
+    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+
+    // Q fragments of query block 0 (B operand of S^T): lane (query l31, half lh) holds Q[q][16 kk + 8 lh .. + 8)
+    f16x8 qf[KK];
+    {
+        const f16* qp = q + (qbase + (size_t)(l31 < Tq ? l31 : 0) * HW) * ld + head * D + lh * 8;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) qf[kk] = l31 < Tq ? *(const f16x8*)(qp + kk * 16) : zero8;
+    }
+    // ---- K and V rows of the live slots, UB passes at a time; dead slots and rows >= T are written as zero and never read
+    //      (their probability is exactly 0, but 0 * NaN from never-written LDS would not be) ----
+    {
+        const int r0 = lane / DC, cc = lane % DC;
+#pragma unroll 1
+        for (int t0 = 0; t0 < ROWS; t0 += UB * RPI) {
+            // UB * RPI divides 32: the rows of one iteration lie in one mask word (wave-uniform; bits >= T are clear)
+            const unsigned mw = (t0 >> 5) == 0 ? m0 : (t0 >> 5) == 1 ? m1 : (t0 >> 5) == 2 ? m2 : m3;
+            f16x8 gk[UB], gv[UB];
+#pragma unroll
+            for (int u = 0; u < UB; ++u) {
+                const int t = t0 + u * RPI + r0;
+                gk[u] = zero8; gv[u] = zero8;
+                if ((mw >> (t & 31)) & 1u) {
+                    const size_t off = (base + (size_t)t * HW) * ldkv + head * D + cc * 8;
+                    gk[u] = *(const f16x8*)(k + off);
+                    gv[u] = *(const f16x8*)(v + off);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UB; ++u) {
+                const int t = t0 + u * RPI + r0;
+                *(f16x8*)&wK[t * KSTR + cc * 8] = gk[u];
+                *(f16x8*)&wV[t * VSTR + cc * 8] = gv[u];
+            }
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this wave's LDS writes are in place
+    __builtin_amdgcn_wave_barrier();
+
+    const float c2 = scale * 1.4426950408889634f;
+    const int tr_off = (((lane & 15) >> 2) + 4 * lh) * VSTR + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+#pragma unroll 1
+    for (int q0 = 0; q0 < Tq; q0 += 32) {
+        // the next block's Q fragments are fetched under this block's arithmetic
+        f16x8 qn[KK];
+        {
+            const int qi = q0 + 32 + l31;
+            const f16* qp = q + (qbase + (size_t)(qi < Tq ? qi : 0) * HW) * ld + head * D + lh * 8;
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) qn[kk] = qi < Tq ? *(const f16x8*)(qp + kk * 16) : zero8;
+        }
+        // the mask words as this lane half sees them: bit (r & 3) + 8 (r >> 2) of ml[kt] = the key slot of score s[kt][r].
+        // q0 >> 20 is 0 (Tq <= 128); it keeps the 16 KT bit tests inside the loop -- hoisted, their lane masks take 32 KT
+        // SGPRs and spill at KT >= 3
+        unsigned ml[KT];
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt)
+            ml[kt] = ((kt == 0 ? m0 : kt == 1 ? m1 : kt == 2 ? m2 : m3) >> (4 * lh)) | (unsigned)(q0 >> 20);
+        // ---- S^T tiles: s[kt][r] = score(key = 32 kt + (r & 3) + 8 (r >> 2) + 4 lh, query = q0 + l31) ----
+        f32x16 s[KT];
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
+            const f16* kp = wK + (kt * 32 + l31) * KSTR + lh * 8;
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) {
+                const f16x8 kf = *(const f16x8*)(kp + kk * 16);
+                s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], s[kt], 0, 0, 0);
+            }
+        }
+        float mx = -1e30f;
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                // every tile: a dead slot can lie anywhere (slots >= T are dead: the host clears their bits)
+                if (!(ml[kt] & (1u << ((r & 3) + 8 * (r >> 2))))) s[kt][r] = -1e30f;
+                mx = fmaxf(mx, s[kt][r]);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float mc = mx * c2;
+        float sum = 0.f;
+        f16x8 pf[KT][2];
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float pr = __builtin_amdgcn_exp2f(fmaf(s[kt][r], c2, -mc));   // dead slots: exp2(-huge) = 0    
+                sum += pr;
+                pf[kt][r >> 3][r & 7] = (f16)pr;
+            }
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = 1.0f / sum;
+
+        // ---- O^T[d][q] += V^T[d][key] P^T[key][q]; k-slot (8 lh + jj) of MFMA (kt, u) = key
+        //      32 kt + 16 u + 4 lh + (jj & 3) + 8 (jj >> 2), identical for both operands ----
+        f32x16 o[DB];
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+            const f16* vp = wV + tr_off + db * 32;
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const f16x4 lo = lds_read_tr4(vp + (kt * 32 + u * 16) * VSTR), hi = lds_read_tr4(vp + (kt * 32 + u * 16 + 8) * VSTR);
+                    const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[kt][u], o[db], 0, 0, 0);
+                }
+        }
+        if (q0 + l31 < Tq) {
+            f16* op = out + (qbase + (size_t)(q0 + l31) * HW) * ldo + head * D;
+#pragma unroll
+            for (int db = 0; db < DB; ++db)
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) {
+                    f16x4 w;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) w[e] = (f16)(o[db][4 * qd + e] * inv);
+                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;
+                }
+        }
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
+    }
+}
+
 // waves per workgroup: as many as keep a workgroup's LDS at or below 42 KB (D = 64) / 37 KB (D = 128), at least one
+template <int D, int KT>
+struct TemporalLongGeom {
+    static constexpr int WPB = D == 64 ? (KT == 1 ? 4 : KT == 2 ? 2 : 1) : (KT == 1 ? 2 : 1);
+    static constexpr int LDS = WPB * 32 * KT * (2 * D + 40) * 2;
+};
+
 template <int D, int KT>
 static int launch_attn_temporal_long(const void* q, const void* k, const void* v, void* out, long long nseq, int T, int HW,
                                      int heads, int ld, int ldkv, int ldo, float scale, hipStream_t st) {
-    constexpr int WPB = D == 64 ? (KT == 1 ? 4 : KT == 2 ? 2 : 1) : (KT == 1 ? 2 : 1);
-    constexpr int LDS = WPB * 32 * KT * (2 * D + 40) * 2;
+    constexpr int WPB = TemporalLongGeom<D, KT>::WPB, LDS = TemporalLongGeom<D, KT>::LDS;
     const long long nwg = (nseq + WPB - 1) / WPB;
     if (nwg > 0x7fffffffLL) return MOFA_EINVAL;
     static LaunchSetup setup;
     if (setup.cus([](int) { return mofa_lds_optin((const void*)attn_temporal_long_kernel<D, KT, WPB>, LDS); }) == 0) return MOFA_ELAUNCH;
     hipLaunchKernelGGL((attn_temporal_long_kernel<D, KT, WPB>), dim3((unsigned)nwg), dim3(64 * WPB), LDS, st, (const f16*)q,
                        (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale);
+    MOFA_CHECK_LAUNCH();
+    return MOFA_OK;
+}
+
+template <int D, int KT>
+static int launch_attn_temporal_long_masked(const void* q, const void* k, const void* v, void* out, long long nseq, int Tq, int T,
+                                            int HW, int heads, int ld, int ldkv, int ldo, float scale, const uint32_t* m,
+                                            hipStream_t st) {
+    constexpr int WPB = TemporalLongGeom<D, KT>::WPB, LDS = TemporalLongGeom<D, KT>::LDS;
+    const long long nwg = (nseq + WPB - 1) / WPB;
+    if (nwg > 0x7fffffffLL) return MOFA_EINVAL;
+    static LaunchSetup setup;
+    if (setup.cus([](int) { return mofa_lds_optin((const void*)attn_temporal_long_masked_kernel<D, KT, WPB>, LDS); }) == 0) return MOFA_ELAUNCH;
+    hipLaunchKernelGGL((attn_temporal_long_masked_kernel<D, KT, WPB>), dim3((unsigned)nwg), dim3(64 * WPB), LDS, st, (const f16*)q,
+                       (const f16*)k, (const f16*)v, (f16*)out, nseq, Tq, T, HW, heads, ld, ldkv, ldo, scale, m[0], m[1], m[2], m[3]);
     MOFA_CHECK_LAUNCH();
     return MOFA_OK;
 }
@@ -774,6 +961,33 @@ extern "C" int mofa_attn_temporal_long_f16(const void* q, const void* k, const v
     hipStream_t st = (hipStream_t)stream;
 #define MOFA_TL_CASE(D_, KT_) \
     if (head_dim == D_ && kt == KT_) return launch_attn_temporal_long<D_, KT_>(q, k, v, out, nseq, T, HW, heads, ld, ldkv, ldo, scale, st);
+    MOFA_TL_CASE(64, 1) MOFA_TL_CASE(64, 2) MOFA_TL_CASE(64, 3) MOFA_TL_CASE(64, 4)
+    MOFA_TL_CASE(128, 1) MOFA_TL_CASE(128, 2) MOFA_TL_CASE(128, 3) MOFA_TL_CASE(128, 4)
+#undef MOFA_TL_CASE
+    return MOFA_EINVAL;
+}
+
+// key_mask: host memory, four words, bit j % 32 of word j / 32 = key slot j exists; NULL = every slot below T.  Bits at and
+// above T are ignored (cleared here: the kernel tests the mask alone).  The words travel as kernel arguments.
+extern "C" int mofa_attn_temporal_long_masked_f16(const void* q, const void* k, const void* v, void* out, int nclips, int Tq,
+                                                  int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo, float scale,
+                                                  const uint32_t* key_mask, mofa_stream_t stream) {
+    if (!q || !k || !v || !out || nclips <= 0 || T < 1 || T > 128 || Tq < 1 || Tq > T || HW <= 0 || heads <= 0) return MOFA_EINVAL;
+    if (head_dim != 64 && head_dim != 128) return MOFA_EINVAL;
+    if (ld <= 0 || ldkv <= 0 || ldo <= 0 || ld % 8 != 0 || ldkv % 8 != 0 || ldo % 8 != 0) return MOFA_EINVAL;
+    uint32_t m[4];
+    for (int w = 0; w < 4; ++w) {
+        const int n = T - 32 * w;                                   // slots of this word below T
+        const uint32_t below = n >= 32 ? 0xffffffffu : n > 0 ? (1u << n) - 1u : 0u;
+        m[w] = (key_mask ? key_mask[w] : 0xffffffffu) & below;
+    }
+    if ((m[0] | m[1] | m[2] | m[3]) == 0) return MOFA_EINVAL;
+    const long long nseq = (long long)nclips * HW * heads;
+    const int kt = (T + 31) / 32;
+    hipStream_t st = (hipStream_t)stream;
+#define MOFA_TL_CASE(D_, KT_) \
+    if (head_dim == D_ && kt == KT_) \
+        return launch_attn_temporal_long_masked<D_, KT_>(q, k, v, out, nseq, Tq, T, HW, heads, ld, ldkv, ldo, scale, m, st);
     MOFA_TL_CASE(64, 1) MOFA_TL_CASE(64, 2) MOFA_TL_CASE(64, 3) MOFA_TL_CASE(64, 4)
     MOFA_TL_CASE(128, 1) MOFA_TL_CASE(128, 2) MOFA_TL_CASE(128, 3) MOFA_TL_CASE(128, 4)
 #undef MOFA_TL_CASE

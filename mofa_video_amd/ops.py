@@ -428,7 +428,8 @@ def attn_spatial(q, k, v, nframes, heads, S, head_dim=64, scale=None, out=None, 
 def attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=None, Tq=None, key_mask=None):
     """k/v hold T frames per clip; q holds Tq <= T (Tq < T: frame-sharded clip with all-gathered K/V).  key_mask: bit j =
     key frame j exists (padding frames of uneven shards in the gathered buffer are masked, never read).
-    T > 32 (up to 128): plain self-attention only (Tq == T, no mask) through mofa_attn_temporal_long_f16."""
+    T > 32 (up to 128): plain self-attention only (Tq == T, no mask) through mofa_attn_temporal_long_f16; the sharded form
+    of such clips is ``attn_temporal_sharded``."""
     Tq = T if Tq is None else Tq
     if T > 32 and (key_mask is not None or Tq != T):
         raise ValueError(f"temporal attention over {T} key frames with a key mask or Tq < T: frame-sharded clips are limited "
@@ -454,6 +455,38 @@ def attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=No
         L.check(lib.mofa_attn_temporal_masked_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, Tq, T, HW, heads, head_dim,
                                                   _ld(q), _ld(k), _ld(out), scale, int(key_mask), L.stream_ptr()),
                 "mofa_attn_temporal_masked_f16")
+    return out
+
+
+def attn_temporal_sharded(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=None, Tq=None, key_mask=None):
+    """``attn_temporal`` for frame-sharded clips of up to 128 key slots: q holds Tq <= T frames, k / v the T slots of the gathered
+    buffer, key_mask (a Python int of up to 128 bits; None = every slot) says which slots exist.  T <= 32 is ``attn_temporal``
+    itself (the same kernels, the same bits); T > 32 runs mofa_attn_temporal_long_masked_f16."""
+    if T <= 32:
+        return attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=head_dim, scale=scale, out=out, Tq=Tq, key_mask=key_mask)
+    Tq = T if Tq is None else Tq
+    lib = L.load()
+    assert _ld(k) == _ld(v)
+    scale = head_dim ** -0.5 if scale is None else scale
+    if out is None:
+        out = torch.empty((nclips * Tq * HW, heads * head_dim), dtype=F16, device=q.device)
+    else:
+        _written(out)
+    words = None
+    if key_mask is not None:
+        m = int(key_mask)
+        if m < 0:
+            raise ValueError("key_mask must be a non-negative integer")
+        words = (C.c_uint32 * 4)(*[(m >> (32 * w)) & 0xffffffff for w in range(4)])     # (bits >= 128 are >= T: ignored)
+    t0 = TIMER.start() if TIMER is not None else None
+    L.check(lib.mofa_attn_temporal_long_masked_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, Tq, T, HW, heads, head_dim,
+                                                   _ld(q), _ld(k), _ld(out), scale, words, L.stream_ptr()),
+            "mofa_attn_temporal_long_masked_f16")
+    if t0 is not None:
+        Cc = heads * head_dim
+        live = T if key_mask is None else bin(int(key_mask) & ((1 << T) - 1)).count("1")
+        TIMER.stop("attn_temporal_long_kernel", t0, flops=4.0 * Tq * live * Cc * nclips * HW,
+                   nbytes=4.0 * nclips * (Tq + live) * HW * Cc)
     return out
 
 

@@ -288,7 +288,14 @@ class ThreadComm:
 class FrameParallel:
     """The per-rank object blocks consult (``Ctx.par``) when a clip's frames are sharded."""
 
-    def __init__(self, layout, comm, p2p=True):
+    def __init__(self, layout, comm, p2p=True, max_key_slots=32):
+        """max_key_slots: the most key slots (frame_ranks x largest shard) the temporal attention takes from the gathered
+        buffer in place, 32 .. 128.  The default of 32 is the T <= 32 masked kernel; above it clips of up to that many frames
+        may be sharded and their attention runs through mofa_attn_temporal_long_masked_f16 (``ops.attn_temporal_sharded``).
+        A layout whose padded slots exceed the limit compacts to T_full frames first."""
+        if isinstance(max_key_slots, bool) or not isinstance(max_key_slots, int) or not 32 <= max_key_slots <= 128:
+            raise ValueError(f"max_key_slots must be an integer in 32 .. 128, got {max_key_slots!r}")
+        self.max_key_slots = max_key_slots
         self.lay, self.comm = layout, comm
         self.T_full, self.T_loc, self.f0, self.f1 = layout.T, layout.T_loc, layout.f0, layout.f1
         self.p2p = p2p
@@ -313,7 +320,7 @@ class FrameParallel:
         all_gather_into_tensor whose input aliases its output slot (K|V exchange) and the batched isend / irecv halo
         exchange -- and compares with what the plain list all_gather delivers.  A path that raises or returns wrong data is
         switched off ON EVERY RANK of the frame group (the verdict is all-reduced), so the run continues on the conservative
-        path (pad + all_gather + compaction, as for more than 32 key slots; all_gather-based halo).  Covers WRONG-DATA failures
+        path (pad + all_gather + compaction, as for more than ``max_key_slots`` key slots; all_gather-based halo).  Covers WRONG-DATA failures
         and exceptions every rank of the group raises alike (an unsupported call); a rank that raises alone while its peers
         are already inside the collective leaves them blocked -- that case ends at the process group's own
         timeout (torch.distributed's default), not in this check.  Returns a dict for the caller to report.  Meant for the
@@ -473,8 +480,8 @@ class FrameParallel:
     # temporal attention K/V ---------------------------------------------------------------------------------
     @property
     def kv_slots(self):
-        """key-frame slots of the gathered K|V buffer (frame_ranks x largest shard); the masked attention entry takes
-        at most 32"""
+        """key-frame slots of the gathered K|V buffer (frame_ranks x largest shard); the masked attention entries take
+        at most ``max_key_slots``"""
         return self.lay.frame_ranks * self.lay.T_max
 
     @property
@@ -529,12 +536,13 @@ class GroupedWindowParallel:
     hands every rank every stepped window (the g ranks of a group hold identical copies; entry 0 of each group is used).
     ``window_layout_costs`` says when this beats the two plain layouts (e.g. 4 windows on 8 ranks: 4 x 2)."""
 
-    def __init__(self, comm, rank, world, ranks_per_group, window_size):
+    def __init__(self, comm, rank, world, ranks_per_group, window_size, max_key_slots=32):
         g = ranks_per_group
         assert world % g == 0 and g >= 2 and g % 2 == 0
         self.comm, self.rank, self.world, self.g = comm, rank, world, g
         self.groups, self.slot = world // g, rank // g
-        self.frame = FrameParallel(Layout(g, rank % g, window_size, base=self.slot * g), comm)
+        self.frame = FrameParallel(Layout(g, rank % g, window_size, base=self.slot * g), comm, max_key_slots=max_key_slots)
+        self.max_key_slots = self.frame.max_key_slots               # (what pipeline._check_call asks a ``parallel`` object for)
 
     @staticmethod
     def layout_of_rank(world, ranks_per_group, window_size):

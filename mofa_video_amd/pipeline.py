@@ -144,7 +144,8 @@ class FlowControlNetPipeline:
         round_latents_to_fp16: round the latents to fp16 after every Euler step, as the reference's fp16 run does.
         max_temporal_frames: the most frames one forward pass may hold (``num_frames``, or ``window_size`` of the window
         loop), 1 .. 128.  Above the default of 32 the temporal attention runs through mofa_attn_temporal_long_f16; clips
-        sharded over ranks (``parallel``) stay limited to 32."""
+        sharded over ranks (``parallel``) stay limited to 32 unless the parallel object was built with ``max_key_slots=`` (up
+        to 128): then to the smaller of the two."""
         if isinstance(max_temporal_frames, bool) or not isinstance(max_temporal_frames, int) \
                 or not 1 <= max_temporal_frames <= MAX_TEMPORAL_FRAMES_LONG:
             raise ValueError(f"max_temporal_frames must be an integer in 1 .. {MAX_TEMPORAL_FRAMES_LONG}, got {max_temporal_frames!r}")
@@ -309,9 +310,14 @@ class FlowControlNetPipeline:
                              f"{limit} (use KeypointFlowControlNetPipeline's window loop for long clips"
                              + (f", or build the pipeline with max_temporal_frames=... up to {MAX_TEMPORAL_FRAMES_LONG})"
                                 if limit < MAX_TEMPORAL_FRAMES_LONG else ")"))
-        if frames_per_forward > MAX_TEMPORAL_FRAMES and self.parallel is not None:
-            raise ValueError(f"{frames_per_forward} frames per forward pass with parallel=...: clips sharded over ranks are limited "
-                             f"to {MAX_TEMPORAL_FRAMES} frames (their gathered keys carry a 32-bit mask); run long clips on one device")
+        if self.parallel is not None:
+            slots = getattr(self.parallel, "max_key_slots", MAX_TEMPORAL_FRAMES)
+            if frames_per_forward > slots and slots == MAX_TEMPORAL_FRAMES:
+                raise ValueError(f"{frames_per_forward} frames per forward pass with parallel=...: clips sharded over ranks are limited "
+                                 f"to {MAX_TEMPORAL_FRAMES} frames (their gathered keys carry a 32-bit mask); run long clips on one device")
+            if frames_per_forward > slots:
+                raise ValueError(f"{frames_per_forward} frames per forward pass with parallel=...: this parallel object takes clips of "
+                                 f"at most max_key_slots = {slots} frames")
 
     def prepare_latents(self, batch_size, num_frames, num_channels_latents, height, width, generator, latents=None):
         shape = (batch_size, num_frames, num_channels_latents // 2, height // 8, width // 8)
