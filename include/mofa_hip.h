@@ -192,6 +192,20 @@ int mofa_attn_temporal_long_f16(const void* q, const void* k, const void* v, voi
 int mofa_attn_temporal_long_masked_f16(const void* q, const void* k, const void* v, void* out,
                                        int nclips, int Tq, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
                                        float scale, const uint32_t* key_mask, mofa_stream_t stream);
+/* Local temporal self-attention over 1 <= T <= 128 frames: mofa_attn_temporal_long_f16 (the same layout, the same kernel
+ * body) under a per-QUERY visibility rule given by two integers, radius >= 0 and 0 <= anchor <= T:
+ *     query frame i sees key frame j  iff  j < anchor  or  |i - j| <= radius
+ * -- a band around the query plus the first `anchor` frames (anchor = 1: the conditioning frame).  Every query sees itself,
+ * so no softmax row is empty; an invisible key has probability exactly 0; radius >= T - 1 (larger values are accepted and mean
+ * "all") or anchor == T makes every key visible.  The two integers travel as kernel arguments.  Precondition: K and V of all
+ * T frames are finite -- an invisible frame is still staged and multiplied by its zero probability, so its inf or NaN would
+ * reach the output (only slots that do not exist are protected, by mofa_attn_temporal_long_masked_f16).  Two equalities hold
+ * bit for bit: with every key visible the output is that of mofa_attn_temporal_long_f16; and row i of the output is row i of
+ * mofa_attn_temporal_long_masked_f16 called with Tq == T and the key mask {j : i sees j}.  MOFA_EINVAL for everything
+ * mofa_attn_temporal_long_f16 refuses and for radius < 0, anchor < 0 or anchor > T -- all checked before any device call. */
+int mofa_attn_temporal_long_local_f16(const void* q, const void* k, const void* v, void* out,
+                                      int nclips, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
+                                      float scale, int radius, int anchor, mofa_stream_t stream);
 /* in-place row softmax of an fp16 [rows][cols] matrix (VAE mid-block attention, 1 head x 512) */
 int mofa_softmax_rows_f16(void* x, int rows, int cols, int ld, mofa_stream_t stream);
 

@@ -147,8 +147,8 @@ class FlowControlNet:
             warped.append(allf)
         return warped
 
-    def make_ctx(self, timestep, encoder_hidden_states, added_time_ids, B, T, base=None, half=None, par=None):
-        return make_ctx(self, timestep, encoder_hidden_states, added_time_ids, B, T, base, half, par)   # blocks.make_ctx
+    def make_ctx(self, timestep, encoder_hidden_states, added_time_ids, B, T, base=None, half=None, par=None, local=None):
+        return make_ctx(self, timestep, encoder_hidden_states, added_time_ids, B, T, base, half, par, local)   # blocks.make_ctx
 
     def _add_warped(self, sample, warped, B):
         rows = warped.shape[0]

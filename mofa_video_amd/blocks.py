@@ -58,13 +58,15 @@ class Ctx:
         self.par = None           # parallel.FrameParallel when this rank holds only frames [f0, f1) of the clip
         self.ctx16_all = None     # fp16 [B_global, cross_dim]: both CFG halves' embeddings (temporal-context quirk)
         self.half = 0             # global CFG-half index of local batch row 0
+        self.local = None         # (radius, anchor) of local temporal attention (ops.attn_temporal_local); None = dense
         self.halves = None        # [Ctx(1, T), Ctx(1, T)] of a B = 2 context whose CFG halves are evaluated separately (pipeline.py)
 
 
-def make_ctx(net, timestep, encoder_hidden_states, added_time_ids, B, T, base=None, half=None, par=None):
+def make_ctx(net, timestep, encoder_hidden_states, added_time_ids, B, T, base=None, half=None, par=None, local=None):
     """The ``Ctx`` of one forward pass of ``net`` (anything with ``time``, ``temb_batch`` and ``device``: the UNet, an adapter).
     B, T = LOCAL batch / frame counts.  half: global CFG-half index when this rank computes one half only
-    (encoder_hidden_states / added_time_ids are then still the global 2-row tensors); par: FrameParallel."""
+    (encoder_hidden_states / added_time_ids are then still the global 2-row tensors); par: FrameParallel; local: (radius,
+    anchor) of local temporal attention -- every temporal layer of the pass attends under it -- or None for dense attention."""
     c = base if base is not None else Ctx(B, T)
     ts = torch.as_tensor(timestep, dtype=torch.float32, device=net.device).reshape(-1)
     ts = ts.expand(B).contiguous() if ts.numel() == 1 else ts.contiguous()
@@ -82,7 +84,9 @@ def make_ctx(net, timestep, encoder_hidden_states, added_time_ids, B, T, base=No
             c.half = half
         else:
             c.ctx16 = ops.cast_f32_to_f16(e)
-    c.par = par
+    if local is not None and par is not None:
+        raise ValueError("local temporal attention of frame-sharded clips: the gathered-key path has no per-query mask")
+    c.par, c.local = par, local
     return c
 
 
@@ -464,7 +468,10 @@ class TransformerSpatioTemporal:
             f = self.ff_in(self.norm_in(h, rowvec=pos, rv_div=HW, rv_mod=T), r1=h, s1=1.0, rowvec=pos, rv=pos_rv)
         if c.par is None:
             q, k, v = self.tattn1.qkv(fn if fn is not None else self.tnorm1(f))
-            a = ops.attn_temporal(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim)
+            if c.local is None:
+                a = ops.attn_temporal(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim)
+            else:
+                a = ops.attn_temporal_local(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim, local=c.local)
         else:
             # this rank holds T of the clip's T_full frames.  The K|V projection writes this shard's slot of the gather
             # buffer, one all_gather_into_tensor (asynchronous, RCCL's stream) fills the other slots while the Q

@@ -15,6 +15,8 @@
 //
 // mofa_attn_temporal_long_f16: the same for 1 <= T <= 128 frames (clips of more than 32 frames per forward pass): ceil(T / 32)
 //   key tiles of K and V in the wave's LDS, one 32-query block at a time with all of its score tiles in registers.
+//   mofa_attn_temporal_long_masked_f16: its form for frame-sharded clips (Tq <= T query frames, a key mask);
+//   mofa_attn_temporal_long_local_f16: its form under a per-query rule (a band round the query plus the first frames).
 
 #include "common.h"
 
@@ -995,7 +997,215 @@ extern "C" int mofa_attn_temporal_long_masked_f16(const void* q, const void* k, 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// In-place row softmax (VAE mid-block attention: 1 head x 512, scores materialised per frame)
+// Local long temporal attention: attn_temporal_long_kernel under a per-QUERY visibility rule given by two wave-uniform
+// integers -- query frame i sees key frame j iff j < anchor or |i - j| <= radius (a band around the query plus the first
+// `anchor` frames; every query sees itself, so no row is empty).  The same staging, LDS layout and fragment algebra: all T
+// frames of K and V are staged (other queries of the sequence need them), a lane owns one query and all KT score tiles, and
+// an invisible score is set to -1e30 before the row maximum, in EVERY tile, together with the key >= T test; softmax and P V
+// are those of the dense kernel operation for operation, so an invisible key has probability exactly 0 and a rule that hides
+// nothing gives the dense kernel's bits.  The rule reaches a lane as KT words built per query block (bit = the key of a score is
+// visible), tested like the masked kernel's words: three VALU instructions per score, 1-7 % over the dense kernel's time.  No
+// key tile is skipped: wave-uniform branches round the dead tiles of a query block cut the block's straight-line code, in which
+// MFMAs and softmax arithmetic overlap, into pieces, and ran 1.25-1.46 x the dense time at KT >= 3.
+// K and V of the clip's frames must be finite: an invisible frame IS read and multiplied by its zero probability.
+// The host passes radius <= 127 and 0 <= anchor <= T.  A kernel of its own for the reason given above the masked kernel.
+// ---------------------------------------------------------------------------------------------------
+template <int D, int KT, int WPB>
+__global__ __launch_bounds__(64 * WPB) void attn_temporal_long_local_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                            const f16* __restrict__ v, f16* __restrict__ out,
+                                                                            long long nseq, int T, int HW, int heads, int ld,
+                                                                            int ldkv, int ldo, float scale, int radius,
+                                                                            int anchor) {
+    constexpr int DC = D / 8;       // 16-byte chunks per row
+    constexpr int KK = D / 16;      // MFMA k-steps of S^T
+    constexpr int DB = D / 32;      // 32-wide output d-blocks
+    constexpr int KSTR = D + 8;     // K row stride in halves (conflict-free ds_read_b128)
+    constexpr int VSTR = D + 32;    // V row stride in halves (see lds_read_tr4)
+    constexpr int ROWS = 32 * KT;   // staged key rows
+    constexpr int RPI = 64 / DC;    // key rows one wave-wide pass of 16-byte chunks covers (8 / 4)
+    constexpr int UB = 4;           // passes in flight: 2 UB 16-byte loads per lane before the first LDS store
+    extern __shared__ __attribute__((aligned(16))) char smem_tl[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long seq = (long long)blockIdx.x * WPB + wave;
+    if (seq >= nseq) return;                                       // (no workgroup barrier below: LDS regions are per wave)
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int head = (int)(seq % heads);
+    const long long bp = seq / heads;
+    const int p = (int)(bp % HW);
+    const int b = (int)(bp / HW);
+    const size_t base = ((size_t)b * T * HW + p);                  // token row of frame 0 (q, k, v and out alike)
+    f16* wK = (f16*)smem_tl + (size_t)wave * (ROWS * (KSTR + VSTR));
+    f16* wV = wK + ROWS * KSTR;
+    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+
+    // Q fragments of query block 0 (B operand of S^T): lane (query l31, half lh) holds Q[q][16 kk + 8 lh .. + 8)
+    f16x8 qf[KK];
+    {
+        const f16* qp = q + (base + (size_t)(l31 < T ? l31 : 0) * HW) * ld + head * D + lh * 8;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) qf[kk] = l31 < T ? *(const f16x8*)(qp + kk * 16) : zero8;
+    }
+    // ---- K and V rows of the T frames, UB passes at a time; rows >= T are written as zero and never read (a key beyond T
+    //      has probability exactly 0, but 0 * NaN from never-written LDS would not be) ----
+    {
+        const int r0 = lane / DC, cc = lane % DC;
+#pragma unroll 1
+        for (int t0 = 0; t0 < ROWS; t0 += UB * RPI) {
+            f16x8 gk[UB], gv[UB];
+#pragma unroll
+            for (int u = 0; u < UB; ++u) {
+                const int t = t0 + u * RPI + r0;
+                gk[u] = zero8; gv[u] = zero8;
+                if (t < T) {
+                    const size_t off = (base + (size_t)t * HW) * ldkv + head * D + cc * 8;
+                    gk[u] = *(const f16x8*)(k + off);
+                    gv[u] = *(const f16x8*)(v + off);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UB; ++u) {
+                const int t = t0 + u * RPI + r0;
+                *(f16x8*)&wK[t * KSTR + cc * 8] = gk[u];
+                *(f16x8*)&wV[t * VSTR + cc * 8] = gv[u];
+            }
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this wave's LDS writes are in place
+    __builtin_amdgcn_wave_barrier();
+
+    const float c2 = scale * 1.4426950408889634f;
+    const int tr_off = (((lane & 15) >> 2) + 4 * lh) * VSTR + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+#pragma unroll 1
+    for (int q0 = 0; q0 < T; q0 += 32) {
+        // the next block's Q fragments are fetched under this block's arithmetic
+        f16x8 qn[KK];
+        {
+            const int qi = q0 + 32 + l31;
+            const f16* qp = q + (base + (size_t)(qi < T ? qi : 0) * HW) * ld + head * D + lh * 8;
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) qn[kk] = qi < T ? *(const f16x8*)(qp + kk * 16) : zero8;
+        }
+        // the visibility of this lane's query as KT words: bit (r & 3) + 8 (r >> 2) of ml[kt] = the key of score s[kt][r] is
+        // visible.  Keys lo .. hi of the band lie inside [0, T) and anchor <= T, so keys >= T are invisible; query rows >= T are
+        // not stored and take the band of row T - 1.  below(n) = the n lowest bits, n clamped to 0 .. 32
+        const int qi = min(q0 + l31, T - 1);
+        const int lo = max(qi - radius, 0), hi1 = min(qi + radius, T - 1) + 1;
+        unsigned ml[KT];
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+            const auto below = [](int n) { return (unsigned)((1ull << min(max(n, 0), 32)) - 1ull); };
+            ml[kt] = (below(anchor - 32 * kt) | (below(hi1 - 32 * kt) & ~below(lo - 32 * kt))) >> (4 * lh);
+        }
+        // ---- S^T tiles: s[kt][r] = score(key = 32 kt + (r & 3) + 8 (r >> 2) + 4 lh, query = q0 + l31) ----
+        f32x16 s[KT];
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
+            const f16* kp = wK + (kt * 32 + l31) * KSTR + lh * 8;
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) {
+                const f16x8 kf = *(const f16x8*)(kp + kk * 16);
+                s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], s[kt], 0, 0, 0);
+            }
+        }
+        float mx = -1e30f;
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                // every tile: an invisible key can lie anywhere (anchor <= T and hi <= T - 1: keys >= T are invisible)
+                if (!(ml[kt] & (1u << ((r & 3) + 8 * (r >> 2))))) s[kt][r] = -1e30f;
+                mx = fmaxf(mx, s[kt][r]);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float mc = mx * c2;
+        float sum = 0.f;
+        f16x8 pf[KT][2];
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float pr = __builtin_amdgcn_exp2f(fmaf(s[kt][r], c2, -mc));   // invisible keys: exp2(-huge) = 0
+                sum += pr;
+                pf[kt][r >> 3][r & 7] = (f16)pr;
+            }
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = 1.0f / sum;
+
+        // ---- O^T[d][q] += V^T[d][key] P^T[key][q]; k-slot (8 lh + jj) of MFMA (kt, u) = key
+        //      32 kt + 16 u + 4 lh + (jj & 3) + 8 (jj >> 2), identical for both operands ----
+        f32x16 o[DB];
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+            const f16* vp = wV + tr_off + db * 32;
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const f16x4 lo = lds_read_tr4(vp + (kt * 32 + u * 16) * VSTR), hi = lds_read_tr4(vp + (kt * 32 + u * 16 + 8) * VSTR);
+                    const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[kt][u], o[db], 0, 0, 0);
+                }
+        }
+        if (q0 + l31 < T) {
+            f16* op = out + (base + (size_t)(q0 + l31) * HW) * ldo + head * D;
+#pragma unroll
+            for (int db = 0; db < DB; ++db)
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) {
+                    f16x4 w;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) w[e] = (f16)(o[db][4 * qd + e] * inv);
+                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;
+                }
+        }
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
+    }
+}
+
+template <int D, int KT>
+static int launch_attn_temporal_long_local(const void* q, const void* k, const void* v, void* out, long long nseq, int T, int HW,
+                                           int heads, int ld, int ldkv, int ldo, float scale, int radius, int anchor,
+                                           hipStream_t st) {
+    constexpr int WPB = TemporalLongGeom<D, KT>::WPB, LDS = TemporalLongGeom<D, KT>::LDS;
+    const long long nwg = (nseq + WPB - 1) / WPB;
+    if (nwg > 0x7fffffffLL) return MOFA_EINVAL;
+    static LaunchSetup setup;
+    if (setup.cus([](int) { return mofa_lds_optin((const void*)attn_temporal_long_local_kernel<D, KT, WPB>, LDS); }) == 0) return MOFA_ELAUNCH;
+    hipLaunchKernelGGL((attn_temporal_long_local_kernel<D, KT, WPB>), dim3((unsigned)nwg), dim3(64 * WPB), LDS, st, (const f16*)q,
+                       (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale, radius, anchor);
+    MOFA_CHECK_LAUNCH();
+    return MOFA_OK;
+}
+
+// query frame i sees key frame j iff j < anchor or |i - j| <= radius; radius > T - 1 means "all" (clamped here: the kernel adds
+// it to a frame index)
+extern "C" int mofa_attn_temporal_long_local_f16(const void* q, const void* k, const void* v, void* out, int nclips, int T, int HW,
+                                                 int heads, int head_dim, int ld, int ldkv, int ldo, float scale, int radius,
+                                                 int anchor, mofa_stream_t stream) {
+    if (!q || !k || !v || !out || nclips <= 0 || T < 1 || T > 128 || HW <= 0 || heads <= 0) return MOFA_EINVAL;
+    if (head_dim != 64 && head_dim != 128) return MOFA_EINVAL;
+    if (ld <= 0 || ldkv <= 0 || ldo <= 0 || ld % 8 != 0 || ldkv % 8 != 0 || ldo % 8 != 0) return MOFA_EINVAL;
+    if (radius < 0 || anchor < 0 || anchor > T) return MOFA_EINVAL;
+    if (radius > 127) radius = 127;
+    const long long nseq = (long long)nclips * HW * heads;
+    const int kt = (T + 31) / 32;
+    hipStream_t st = (hipStream_t)stream;
+#define MOFA_TL_CASE(D_, KT_) \
+    if (head_dim == D_ && kt == KT_) \
+        return launch_attn_temporal_long_local<D_, KT_>(q, k, v, out, nseq, T, HW, heads, ld, ldkv, ldo, scale, radius, anchor, st);
+    MOFA_TL_CASE(64, 1) MOFA_TL_CASE(64, 2) MOFA_TL_CASE(64, 3) MOFA_TL_CASE(64, 4)
+    MOFA_TL_CASE(128, 1) MOFA_TL_CASE(128, 2) MOFA_TL_CASE(128, 3) MOFA_TL_CASE(128, 4)
+#undef MOFA_TL_CASE
+    return MOFA_EINVAL;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// In-place row softmax(VAE mid-block attention: 1 head x 512, scores materialised per frame)
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void softmax_rows_kernel(f16* __restrict__ x, int cols, int ld) {
     __shared__ float red[8];

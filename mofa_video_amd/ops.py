@@ -490,6 +490,37 @@ def attn_temporal_sharded(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None
     return out
 
 
+def attn_temporal_local(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=None, Tq=None, key_mask=None, local=None):
+    """``attn_temporal`` under a per-query visibility rule, local = (radius, anchor): query frame i sees key frame j iff
+    j < anchor or |i - j| <= radius (radius >= 0, 0 <= anchor <= T; radius >= T - 1 or anchor == T hides nothing), through
+    mofa_attn_temporal_long_local_f16 for every 1 <= T <= 128, T <= 32 included.  Self-attention only: ``Tq`` / ``key_mask``
+    (the parameters of ``attn_temporal``, kept so that a caller who switches entry points is told) are refused -- the
+    gathered-key path of frame-sharded clips has no per-query mask.  K and V of all T frames must be finite: an invisible frame
+    is still read and weighted by an exact 0.  An entry point of its own: ``attn_temporal`` / ``attn_temporal_sharded`` keep
+    their signatures (the CPU stand-ins mirror them parameter for parameter)."""
+    if key_mask is not None or Tq is not None:
+        raise ValueError("local temporal attention takes no key_mask and no Tq: the gathered-key path of frame-sharded clips has "
+                         "no per-query mask")
+    if local is None:
+        raise ValueError("local=(radius, anchor) is required; dense temporal attention is attn_temporal")
+    radius, anchor = (int(x) for x in local)
+    lib = L.load()
+    assert _ld(k) == _ld(v)
+    scale = head_dim ** -0.5 if scale is None else scale
+    if out is None:
+        out = torch.empty((nclips * T * HW, heads * head_dim), dtype=F16, device=q.device)
+    else:
+        _written(out)
+    t0 = TIMER.start() if TIMER is not None else None
+    L.check(lib.mofa_attn_temporal_long_local_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, T, HW, heads, head_dim,
+                                                  _ld(q), _ld(k), _ld(out), scale, radius, anchor, L.stream_ptr()),
+            "mofa_attn_temporal_long_local_f16")
+    if t0 is not None:
+        Cc = heads * head_dim
+        TIMER.stop("attn_temporal_long_kernel", t0, flops=4.0 * T * T * Cc * nclips * HW, nbytes=8.0 * nclips * T * HW * Cc)
+    return out
+
+
 def softmax_rows_(x):
     lib = L.load()
     L.check(lib.mofa_softmax_rows_f16(L.ptr(x), x.shape[0], x.shape[1], _ld(x), L.stream_ptr()), "mofa_softmax_rows_f16")

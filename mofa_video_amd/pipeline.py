@@ -62,6 +62,31 @@ class FlowControlNetPipelineOutput:
 
 MAX_TEMPORAL_FRAMES = 32        # mofa_attn_temporal_f16 holds one clip's keys in one score tile: the default limit per forward pass
 MAX_TEMPORAL_FRAMES_LONG = 128  # mofa_attn_temporal_long_f16 (four key tiles): what max_temporal_frames=... can raise it to
+
+
+def _temporal_window(value):
+    """the ``temporal_window`` keyword -> None or (radius, anchor): an int is (radius, 1) -- frame 0, the conditioning frame,
+    stays visible to every query.  anchor <= T is checked per call, where T is known"""
+    def whole(x):
+        return isinstance(x, int) and not isinstance(x, bool)
+    if value is None:
+        return None
+    if whole(value) and 0 <= value:
+        return (value, 1)
+    if isinstance(value, (tuple, list)) and len(value) == 2 and all(whole(x) for x in value) and value[0] >= 0 \
+            and 0 <= value[1] <= MAX_TEMPORAL_FRAMES_LONG:
+        return (value[0], value[1])
+    raise ValueError("temporal_window must be None, an integer radius >= 0 or (radius >= 0, anchor in 0 .. "
+                     f"{MAX_TEMPORAL_FRAMES_LONG}), got {value!r}")
+
+
+def _shards_frames(parallel):
+    """does this ``parallel`` object shard the frames of a forward pass (FrameParallel, or the groups of a
+    GroupedWindowParallel)?  A CFG split alone and WindowParallel do not"""
+    lay = getattr(getattr(parallel, "frame", parallel), "lay", None)
+    return lay is not None and bool(lay.sharded_frames)
+
+
 GRAPH_STEPS_DEFAULT = os.environ.get("MOFA_GRAPH_STEPS", "0") == "1"
 
 
@@ -138,18 +163,26 @@ class _Step:
 
 class FlowControlNetPipeline:
     def __init__(self, vae=None, image_encoder=None, unet=None, controlnet=None, scheduler=None,
-                 feature_extractor=None, parallel=None, round_latents_to_fp16=False, max_temporal_frames: int = MAX_TEMPORAL_FRAMES):
+                 feature_extractor=None, parallel=None, round_latents_to_fp16=False, max_temporal_frames: int = MAX_TEMPORAL_FRAMES,
+                 temporal_window=None):
         """parallel: optional ``parallel.FrameParallel`` -- this process then computes one CFG half / one frame shard
         of every clip (mofa_video_amd/parallel.py); all ranks must call the pipeline with identical inputs.
         round_latents_to_fp16: round the latents to fp16 after every Euler step, as the reference's fp16 run does.
         max_temporal_frames: the most frames one forward pass may hold (``num_frames``, or ``window_size`` of the window
         loop), 1 .. 128.  Above the default of 32 the temporal attention runs through mofa_attn_temporal_long_f16; clips
         sharded over ranks (``parallel``) stay limited to 32 unless the parallel object was built with ``max_key_slots=`` (up
-        to 128): then to the smaller of the two."""
+        to 128): then to the smaller of the two.
+        temporal_window: None (dense temporal attention, the default: today's launches), an integer radius, or (radius,
+        anchor): local temporal attention in every temporal layer of the UNet and the adapters -- query frame i sees key
+        frame j iff j < anchor or |i - j| <= radius (mofa_attn_temporal_long_local_f16); an integer means (radius, 1), frame 0
+        being the conditioning frame.  In the Keypoint window loop the rule applies inside every window (a window is one
+        forward pass of window_size frames).  Not available with a ``parallel`` object that shards frames.  Nothing is claimed
+        about what the released checkpoints produce under it."""
         if isinstance(max_temporal_frames, bool) or not isinstance(max_temporal_frames, int) \
                 or not 1 <= max_temporal_frames <= MAX_TEMPORAL_FRAMES_LONG:
             raise ValueError(f"max_temporal_frames must be an integer in 1 .. {MAX_TEMPORAL_FRAMES_LONG}, got {max_temporal_frames!r}")
         self.max_temporal_frames = max_temporal_frames
+        self.temporal_window = _temporal_window(temporal_window)
         self.vae, self.image_encoder, self.unet, self.controlnet = vae, image_encoder, unet, controlnet
         self.scheduler, self.feature_extractor = scheduler, feature_extractor
         self.vae_scale_factor = 8
@@ -187,7 +220,8 @@ class FlowControlNetPipeline:
                                             if k in EulerDiscreteScheduler().config})
         except OSError:
             sch = EulerDiscreteScheduler()
-        names = ("face_controlnet", "drag_controlnet", "parallel", "round_latents_to_fp16", "feature_extractor", "max_temporal_frames")
+        names = ("face_controlnet", "drag_controlnet", "parallel", "round_latents_to_fp16", "feature_extractor", "max_temporal_frames",
+                 "temporal_window")
         kw = {k: v for k, v in modules.items() if k in names}
         if controlnet is not None:
             kw["controlnet"] = controlnet
@@ -199,7 +233,7 @@ class FlowControlNetPipeline:
         (``drive`` runs it through; blocks.run_lockstep interleaves it with the UNet's encoder) -> (12 residuals, mid residual)"""
         res = []
         for net, ctx, cond, scale in adapters:
-            net.make_ctx(t, emb, added_time_ids, Bl, Tl, base=ctx, half=half, par=fpar)
+            net.make_ctx(t, emb, added_time_ids, Bl, Tl, base=ctx, half=half, par=fpar, local=self.temporal_window)
             res.append((yield from net.forward_layers(x_loc, ctx, h, w, cond, scale)))
         down, mid = res[0]
         if len(res) == 2:
@@ -207,7 +241,7 @@ class FlowControlNetPipeline:
         return down, mid
 
     def _encoder_layers(self, x_loc, t, emb, added_time_ids, Bl, Tl, half, fpar, h, w, c_un):
-        self.unet.make_ctx(t, emb, added_time_ids, Bl, Tl, base=c_un, half=half, par=fpar)
+        self.unet.make_ctx(t, emb, added_time_ids, Bl, Tl, base=c_un, half=half, par=fpar, local=self.temporal_window)
         return (yield from self.unet.encode_layers(x_loc, c_un, h, w))
 
     def _denoise_forward(self, x_loc, t, emb, added_time_ids, Bl, Tl, half, fpar, h, w, adapters, c_un, masks=None):
@@ -221,7 +255,7 @@ class FlowControlNetPipeline:
         trunks = self._trunk_layers(adapters, masks, *net_args)
         if not self.overlap_adapter or (fpar is not None and not fpar.two_streams):
             down, mid = drive(trunks)
-            unet.make_ctx(t, emb, added_time_ids, Bl, Tl, base=c_un, half=half, par=fpar)
+            unet.make_ctx(t, emb, added_time_ids, Bl, Tl, base=c_un, half=half, par=fpar, local=self.temporal_window)
             return unet.forward_tokens(x_loc, c_un, h, w, down, mid)
         cur = torch.cuda.current_stream(self.device)
         if self._adapter_stream is None:
@@ -231,7 +265,7 @@ class FlowControlNetPipeline:
         if fpar is None:
             with torch.cuda.stream(side):
                 down, mid = drive(trunks)
-            unet.make_ctx(t, emb, added_time_ids, Bl, Tl, base=c_un, half=half, par=fpar)
+            unet.make_ctx(t, emb, added_time_ids, Bl, Tl, base=c_un, half=half, par=fpar, local=self.temporal_window)
             enc = unet.encode_tokens(x_loc, c_un, h, w)
         else:
             # Frame-sharded ranks: trunk(s) and UNet encoder still overlap on two HIP streams, but both issue collectives, and all
@@ -277,7 +311,8 @@ class FlowControlNetPipeline:
         for hf, st in enumerate((cur, side)):
             with torch.cuda.stream(st):
                 ch = c_un.halves[hf]
-                unet.make_ctx(t[hf:hf + 1] if torch.is_tensor(t) else t, emb, added_time_ids, 1, Tl, base=ch, half=hf, par=None)
+                unet.make_ctx(t[hf:hf + 1] if torch.is_tensor(t) else t, emb, added_time_ids, 1, Tl, base=ch, half=hf, par=None,
+                              local=self.temporal_window)
                 outs[hf] = unet.decode_tokens((_rows_of(sample, hf), [_rows_of(k, hf) for k in skips], counts, Hm, Wm), ch,
                                               [_rows_of(r, hf) for r in down], _rows_of(mid, hf))
         cur.wait_stream(side)
@@ -304,6 +339,13 @@ class FlowControlNetPipeline:
                              "own forward accepts: its controlnet_condition / added_time_ids are not repeated)")
         if not max_guidance_scale > 1.0:
             raise ValueError("the reference pipeline is only well-defined with classifier-free guidance on")
+        if self.temporal_window is not None:
+            if _shards_frames(self.parallel):
+                raise ValueError("temporal_window=... with a parallel object that shards frames: the gathered-key path of "
+                                 "frame-sharded clips has no per-query mask (a CFG split alone and WindowParallel are fine)")
+            if self.temporal_window[1] > frames_per_forward:
+                raise ValueError(f"temporal_window anchor {self.temporal_window[1]} exceeds the {frames_per_forward} frames of a "
+                                 "forward pass")
         limit = self.max_temporal_frames
         if frames_per_forward > limit:
             raise ValueError(f"{frames_per_forward} frames per forward pass: the temporal attention kernel handles at most "
@@ -542,9 +584,10 @@ def _blend_residuals(df, mf, dd, md, masks, nframes):
 class HybridFlowControlNetPipeline(FlowControlNetPipeline):
     def __init__(self, vae=None, image_encoder=None, unet=None, face_controlnet=None, drag_controlnet=None,
                  scheduler=None, feature_extractor=None, parallel=None, round_latents_to_fp16=False,
-                 max_temporal_frames: int = MAX_TEMPORAL_FRAMES):
+                 max_temporal_frames: int = MAX_TEMPORAL_FRAMES, temporal_window=None):
         super().__init__(vae, image_encoder, unet, face_controlnet, scheduler, feature_extractor, parallel=parallel,
-                         round_latents_to_fp16=round_latents_to_fp16, max_temporal_frames=max_temporal_frames)
+                         round_latents_to_fp16=round_latents_to_fp16, max_temporal_frames=max_temporal_frames,
+                         temporal_window=temporal_window)
         self.face_controlnet, self.drag_controlnet = face_controlnet, drag_controlnet
 
     @torch.no_grad()
@@ -774,9 +817,10 @@ class KeypointFlowControlNetPipeline(FlowControlNetPipeline):
 
     def __init__(self, vae=None, image_encoder=None, unet=None, controlnet=None, scheduler=None, feature_extractor=None,
                  parallel=None, round_latents_to_fp16=False, drag_controlnet=None, overlap_decode=True,
-                 max_temporal_frames: int = MAX_TEMPORAL_FRAMES):
+                 max_temporal_frames: int = MAX_TEMPORAL_FRAMES, temporal_window=None):
         super().__init__(vae, image_encoder, unet, controlnet, scheduler, feature_extractor, parallel=parallel,
-                         round_latents_to_fp16=round_latents_to_fp16, max_temporal_frames=max_temporal_frames)
+                         round_latents_to_fp16=round_latents_to_fp16, max_temporal_frames=max_temporal_frames,
+                         temporal_window=temporal_window)
         self.drag_controlnet = drag_controlnet
         self.overlap_decode = overlap_decode
 

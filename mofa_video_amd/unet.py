@@ -77,8 +77,8 @@ class UNetSpatioTemporalConditionControlNetModel:
         return cls(checkpoint.load_state_dict(path, variant), cfg, device)
 
     # ------------------------------------------------------------------------------------------------
-    def make_ctx(self, timestep, encoder_hidden_states, added_time_ids, B, T, base=None, half=None, par=None):
-        return make_ctx(self, timestep, encoder_hidden_states, added_time_ids, B, T, base, half, par)   # blocks.make_ctx
+    def make_ctx(self, timestep, encoder_hidden_states, added_time_ids, B, T, base=None, half=None, par=None, local=None):
+        return make_ctx(self, timestep, encoder_hidden_states, added_time_ids, B, T, base, half, par, local)   # blocks.make_ctx
 
     def forward_tokens(self, x, c, H, W, down_res, mid_res):
         """x: fp16 [B*T*H*W, in_ld] (channels >= in_channels zero); down_res: 12 token tensors; mid_res: token
