@@ -216,17 +216,21 @@ int mofa_softmax_rows_f16(void* x, int rows, int cols, int ld, mofa_stream_t str
  * Replaces nn.GroupNorm + SiLU in diffusers ResnetBlock2D / TemporalResnetBlock /
  * TransformerSpatioTemporalModel.norm / conv_norm_out (unet_..._controlnet.py:236).
  * ---------------------------------------------------------------------------------------- */
-/* workspace `part`: fp32 [nframes][nparts][32][2], nparts = mofa_gn_nparts(HW, C) */
+/* workspace `part`: fp32 [nframes][nparts][32][2], nparts = mofa_gn_nparts(HW, C).
+ * Every entry point below returns MOFA_EINVAL without a launch unless nframes > 0, HW > 0 (where it takes one), 0 < C,
+ * C % 32 == 0 (mofa_affine_act_f16: C % 8 == 0), frames_per_stat > 0 divides nframes and every ld is a multiple of 8;
+ * the entry points that stage C channels in LDS (partial, apply, apply_gathered) also want C <= 4096. */
 int mofa_gn_nparts(int HW, int C);
 int mofa_gn_partial_f16(const void* x, float* part, int nframes, int HW, int C, int ldx, mofa_stream_t stream);
 /* the same `part` entries from the pair sums an implicit-GEMM epilogue emitted (mofa_igemm_args.stats: fp32 [nframes * HW / 64][C]),
  * 64-row blocks dealt to the nparts entries of a frame in order, fixed summation order; HW % 64 == 0, (C / 32) even */
 int mofa_gn_partial_from_stats(const float* stats, float* part, int nframes, int HW, int C, mofa_stream_t stream);
-/* frames_per_stat = 1 (spatial) or T (temporal); writes scale/shift fp32 [nframes][C] */
+/* frames_per_stat = 1 (spatial) or T (temporal); writes scale/shift fp32 [nframes][C].  HW > 0, C > 0, C % 32 == 0 */
 int mofa_gn_finalize(const float* part, const float* gamma, const float* beta, float* scale, float* shift,
                      int nframes, int HW, int C, int frames_per_stat, float eps, mofa_stream_t stream);
 /* split form for frame-sharded clips: partials -> fp64 [nstat][32][2] (sum, sum of squares); the caller all-reduces
- * them over the ranks holding the clip's other frames, then finalizes with the global per-group element count */
+ * them over the ranks holding the clip's other frames, then finalizes with the global per-group element count
+ * (mofa_gn_reduce: HW > 0, C > 0, C % 32 == 0; mofa_gn_finalize_sums: C > 0, C % 32 == 0, count_per_group > 0) */
 int mofa_gn_reduce(const float* part, double* sums, int nframes, int HW, int C, int frames_per_stat, mofa_stream_t stream);
 int mofa_gn_finalize_sums(const double* sums, const float* gamma, const float* beta, float* scale, float* shift,
                           int nframes, int C, int frames_per_stat, double count_per_group, float eps,
@@ -234,21 +238,23 @@ int mofa_gn_finalize_sums(const double* sums, const float* gamma, const float* b
 /* fused finalize + apply (single-rank path): every workgroup combines the partial sums of its statistics set itself (fp64,
  * fixed order) and applies y = (x - mean) * rstd * gamma + beta, optional SiLU -- no scale / shift buffers, no finalize launch.
  * Meant for frames_per_stat * mofa_gn_nparts(HW, C) <= 512 entries (100 KB of partials re-read per workgroup from L2).
- * C <= 4096 (the same limit as mofa_gn_partial_f16), C % 32 == 0. */
+ * 0 < C <= 4096 (the same limit as mofa_gn_partial_f16), C % 32 == 0. */
 int mofa_gn_apply_f16(const void* x, const float* part, const float* gamma, const float* beta, void* y,
                       int nframes, int HW, int C, int ldx, int ldy, int frames_per_stat, float eps, int silu,
                       mofa_stream_t stream);
 /* the same for a statistics set whose frames are sharded over ranks (new work; the reference is single-GPU): `part_all` = the
  * all-gathered partials of the WHOLE set, `nentries` x [32][2] fp32 (zero entries for padding frames), combined by every
  * workgroup in entry order; `count_per_group` = elements per group over the whole set.  Applies that one set to the `nframes`
- * frames of x (the rank's own frames, or a halo frame received raw from a neighbour shard).  C <= 4096, nentries <= 4096. */
+ * frames of x (the rank's own frames, or a halo frame received raw from a neighbour shard).  0 < C <= 4096, C % 32 == 0,
+ * 0 < nentries <= 4096, count_per_group > 0. */
 int mofa_gn_apply_gathered_f16(const void* x, const float* part_all, int nentries, double count_per_group,
                                const float* gamma, const float* beta, void* y, int nframes, int HW, int C,
                                int ldx, int ldy, float eps, int silu, mofa_stream_t stream);
-/* y = x*scale[frame][c] + shift[frame][c]; optional SiLU */
+/* y = x*scale[frame][c] + shift[frame][c]; optional SiLU.  C > 0, C % 8 == 0 */
 int mofa_affine_act_f16(const void* x, const float* scale, const float* shift, void* y,
                         int nframes, int HW, int C, int ldx, int ldy, int silu, mofa_stream_t stream);
-/* LayerNorm over C per token (eps, affine); optional pre-add of rowvec[(m / rv_div) % rv_mod][C] */
+/* LayerNorm over C per token (eps, affine); optional pre-add of rowvec[(m / rv_div) % rv_mod][C].  0 < C <= 1280, C % 8 == 0,
+ * ld* % 8 == 0; with a row vector rv_div > 0 and rv_mod > 0 */
 int mofa_layernorm_f16(const void* x, const float* gamma, const float* beta, void* y, int M, int C,
                        int ldx, int ldy, float eps, const float* rowvec, int rv_div, int rv_mod,
                        mofa_stream_t stream);

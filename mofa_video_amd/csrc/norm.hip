@@ -199,8 +199,8 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
 
 extern "C" int mofa_gn_finalize(const float* part, const float* gamma, const float* beta, float* scale, float* shift,
                                 int nframes, int HW, int C, int frames_per_stat, float eps, mofa_stream_t stream) {
-    if (!part || !gamma || !beta || !scale || !shift || nframes <= 0 || frames_per_stat <= 0 ||
-        nframes % frames_per_stat != 0 || C % 32 != 0)
+    if (!part || !gamma || !beta || !scale || !shift || nframes <= 0 || HW <= 0 || frames_per_stat <= 0 ||
+        nframes % frames_per_stat != 0 || C <= 0 || C % 32 != 0)
         return MOFA_EINVAL;
     const int nparts = mofa_gn_nparts(HW, C);
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(nframes / frames_per_stat), dim3(256), 0, (hipStream_t)stream, part,
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void gn_reduce_kernel(const float* __restrict_
 }
 extern "C" int mofa_gn_reduce(const float* part, double* sums, int nframes, int HW, int C, int frames_per_stat,
                               mofa_stream_t stream) {
-    if (!part || !sums || nframes <= 0 || frames_per_stat <= 0 || nframes % frames_per_stat != 0 || C % 32 != 0)
+    if (!part || !sums || nframes <= 0 || HW <= 0 || frames_per_stat <= 0 || nframes % frames_per_stat != 0 || C <= 0 || C % 32 != 0)
         return MOFA_EINVAL;
     hipLaunchKernelGGL(gn_reduce_kernel, dim3(nframes / frames_per_stat), dim3(256), 0, (hipStream_t)stream, part, sums,
                        frames_per_stat, mofa_gn_nparts(HW, C));
@@ -273,7 +273,7 @@ extern "C" int mofa_gn_finalize_sums(const double* sums, const float* gamma, con
                                      float* shift, int nframes, int C, int frames_per_stat, double count_per_group,
                                      float eps, mofa_stream_t stream) {
     if (!sums || !gamma || !beta || !scale || !shift || nframes <= 0 || frames_per_stat <= 0 ||
-        nframes % frames_per_stat != 0 || C % 32 != 0 || count_per_group <= 0)
+        nframes % frames_per_stat != 0 || C <= 0 || C % 32 != 0 || count_per_group <= 0)
         return MOFA_EINVAL;
     hipLaunchKernelGGL(gn_finalize_sums_kernel, dim3(nframes / frames_per_stat), dim3(256), 0, (hipStream_t)stream, sums,
                        gamma, beta, scale, shift, C, frames_per_stat, count_per_group, eps);
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const f16* __restrict__
 
 extern "C" int mofa_affine_act_f16(const void* x, const float* scale, const float* shift, void* y, int nframes, int HW,
                                    int C, int ldx, int ldy, int silu, mofa_stream_t stream) {
-    if (!x || !scale || !shift || !y || nframes <= 0 || HW <= 0 || C % 8 != 0 || ldx % 8 != 0 || ldy % 8 != 0)
+    if (!x || !scale || !shift || !y || nframes <= 0 || HW <= 0 || C <= 0 || C % 8 != 0 || ldx % 8 != 0 || ldy % 8 != 0)
         return MOFA_EINVAL;
     const long long nvec = (long long)nframes * HW * (C / 8);
     long long nb = (nvec + 255) / 256;
@@ -441,7 +441,7 @@ extern "C" int mofa_gn_apply_f16(const void* x, const float* part, const float* 
                                  int HW, int C, int ldx, int ldy, int frames_per_stat, float eps, int silu,
                                  mofa_stream_t stream) {
     if (!x || !part || !gamma || !beta || !y || nframes <= 0 || HW <= 0 || frames_per_stat <= 0 ||
-        nframes % frames_per_stat != 0 || C % 32 != 0 || C % 8 != 0 || C > 4096 || ldx % 8 != 0 || ldy % 8 != 0)
+        nframes % frames_per_stat != 0 || C <= 0 || C % 32 != 0 || C % 8 != 0 || C > 4096 || ldx % 8 != 0 || ldy % 8 != 0)
         return MOFA_EINVAL;                                  // C <= 4096 as mofa_gn_partial_f16 (C * 8 B of dynamic + 8.5 KB static LDS)
     const int nparts = mofa_gn_nparts(HW, C);
     const int rpw = gn_apply_rows_per_wg(HW, C, nframes, frames_per_stat * nparts);
@@ -463,7 +463,7 @@ extern "C" int mofa_gn_apply_gathered_f16(const void* x, const float* part_all, 
                                           const float* gamma, const float* beta, void* y, int nframes, int HW, int C, int ldx,
                                           int ldy, float eps, int silu, mofa_stream_t stream) {
     if (!x || !part_all || !gamma || !beta || !y || nframes <= 0 || HW <= 0 || nentries <= 0 || nentries > 4096 ||
-        count_per_group <= 0 || C % 32 != 0 || C % 8 != 0 || C > 4096 || ldx % 8 != 0 || ldy % 8 != 0)
+        count_per_group <= 0 || C <= 0 || C % 32 != 0 || C % 8 != 0 || C > 4096 || ldx % 8 != 0 || ldy % 8 != 0)
         return MOFA_EINVAL;
     // (a rank's few frames against the whole clip's gathered entries: about 64 K elements per workgroup, at least 1 024 workgroups)
     int rpw = (65536 + C - 1) / C;

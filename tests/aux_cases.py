@@ -100,6 +100,56 @@ def inputs_of(r):
     return {k: (r.placed[k].before().cpu() if k in r.placed else v) for k, v in r.kwargs.items()}
 
 
+def check_want(what, g, w, accumulate=False):
+    """one output ``g`` against its ``Want`` (or the int / None / object it must be) -> (worst err / bound, [messages]);
+    ``accumulate``: add to the OFF_ROUNDING entry of ``what`` (an output checked in row chunks), not replace it"""
+    errs, worst = [], 0.0
+    if not isinstance(w, Want):
+        if not (g is w or (not torch.is_tensor(g) and g == w)):
+            errs.append(f"{what}: {g!r} returned, {w!r} expected")
+        return worst, errs
+    want = w.bits if w.bits is not None else w.ref
+    if not torch.is_tensor(g) or g.shape != want.shape or (w.bits is not None and g.dtype != want.dtype):
+        errs.append(f"{what}: {getattr(g, 'shape', g)} / {getattr(g, 'dtype', None)} returned, {tuple(want.shape)} expected")
+        return worst, errs
+    if w.bits is not None:
+        n = int((oc.bits(g) != oc.bits(want)).sum())
+        if n:
+            worst = INF
+            first = torch.nonzero(oc.bits(g) != oc.bits(want))[0].tolist()
+            errs.append(f"{what}: {n} / {g.numel()} elements are not bit-equal, first at {first}: {g[tuple(first)].item()!r} "
+                        f"for {want[tuple(first)].item()!r}")
+        return worst, errs
+    gd = g.double()
+    if w.inf is None:                                                # (no mask to apply: a 40 M element output is not gathered four times)
+        inf, sel = torch.zeros((), dtype=torch.bool), (lambda t: t.reshape(-1))
+    else:
+        inf, sel = w.inf, (lambda t: t[~w.inf])
+        if bool((gd[inf] != w.ref[inf]).any()):
+            errs.append(f"{what}: {int((gd[inf] != w.ref[inf]).sum())} of the {int(inf.sum())} overflowing elements are not the same-signed inf")
+    if not bool(torch.isfinite(sel(gd)).all()):
+        bad = ~torch.isfinite(gd) & ~inf
+        errs.append(f"{what}: {int(bad.sum())} non-finite elements, first at {torch.nonzero(bad)[0].tolist()}")
+        return INF, errs
+    err = sel((gd - w.ref).abs())
+    bound = sel((w.bound if torch.is_tensor(w.bound) else torch.full(gd.shape, float(w.bound), dtype=F64)).expand(gd.shape))
+    ratio = torch.where(bound > 0, err / bound.clamp(min=1e-300), torch.where(err > 0, torch.full_like(err, INF), torch.zeros_like(err)))
+    if ratio.numel():
+        worst = max(worst, ratio.max().item())
+        if ratio.max().item() > 1.0:
+            i = int(ratio.argmax())
+            errs.append(f"{what}: {int((ratio > 1).sum())} / {ratio.numel()} elements out of bound, worst err {err[i].item():.4e} "
+                        f"= {ratio[i].item():.3f} x its bound {bound[i].item():.4e}")
+    once = (round16(w.ref) if g.dtype == F16 else w.ref.float()).double()
+    n0, m0 = OFF_ROUNDING.get(what, (0, 0)) if accumulate else (0, 0)
+    OFF_ROUNDING[what] = (n0 + int(sel(gd != once).sum()), m0 + sel(gd).numel())
+    if w.exact is not None and bool(w.exact.any()):
+        n = int((gd[w.exact] != once[w.exact]).sum())
+        if n:
+            errs.append(f"{what}: {n} of the {int(w.exact.sum())} elements that must be exact are not")
+    return worst, errs
+
+
 def check_run(case, r):
     """-> (worst err / bound over the bounded outputs, [messages]): guards, then every output against ``case.ref``"""
     errs = list(r.guard_errors())
@@ -108,47 +158,8 @@ def check_run(case, r):
     if len(wants) != len(outs):
         return INF, errs + [f"{case.id}: {len(outs)} outputs {[o[0] for o in outs]}, {len(wants)} expected"]
     for (label, g, _), w in zip(outs, wants):
-        what = f"{case.id} {label}"
-        if not isinstance(w, Want):
-            if not (g is w or (not torch.is_tensor(g) and g == w)):
-                errs.append(f"{what}: {g!r} returned, {w!r} expected")
-            continue
-        want = w.bits if w.bits is not None else w.ref
-        if not torch.is_tensor(g) or g.shape != want.shape or (w.bits is not None and g.dtype != want.dtype):
-            errs.append(f"{what}: {getattr(g, 'shape', g)} / {getattr(g, 'dtype', None)} returned, {tuple(want.shape)} expected")
-            continue
-        if w.bits is not None:
-            n = int((oc.bits(g) != oc.bits(want)).sum())
-            if n:
-                worst = INF
-                first = torch.nonzero(oc.bits(g) != oc.bits(want))[0].tolist()
-                errs.append(f"{what}: {n} / {g.numel()} elements are not bit-equal, first at {first}: {g[tuple(first)].item()!r} "
-                            f"for {want[tuple(first)].item()!r}")
-            continue
-        gd = g.double()
-        inf = w.inf if w.inf is not None else torch.zeros(gd.shape, dtype=torch.bool)
-        if bool((gd[inf] != w.ref[inf]).any()):
-            errs.append(f"{what}: {int((gd[inf] != w.ref[inf]).sum())} of the {int(inf.sum())} overflowing elements are not the same-signed inf")
-        if not bool(torch.isfinite(gd[~inf]).all()):
-            worst = INF
-            bad = ~torch.isfinite(gd) & ~inf
-            errs.append(f"{what}: {int(bad.sum())} non-finite elements, first at {torch.nonzero(bad)[0].tolist()}")
-            continue
-        err = (gd - w.ref).abs()[~inf]
-        bound = (w.bound if torch.is_tensor(w.bound) else torch.full(gd.shape, float(w.bound), dtype=F64)).expand(gd.shape)[~inf]
-        ratio = torch.where(bound > 0, err / bound.clamp(min=1e-300), torch.where(err > 0, torch.full_like(err, INF), torch.zeros_like(err)))
-        if ratio.numel():
-            worst = max(worst, ratio.max().item())
-            if ratio.max().item() > 1.0:
-                i = int(ratio.argmax())
-                errs.append(f"{what}: {int((ratio > 1).sum())} / {ratio.numel()} elements out of bound, worst err {err[i].item():.4e} "
-                            f"= {ratio[i].item():.3f} x its bound {bound[i].item():.4e}")
-        once = (round16(w.ref) if g.dtype == F16 else w.ref.float()).double()
-        OFF_ROUNDING[what] = (int((gd != once)[~inf].sum()), int((~inf).sum()))
-        if w.exact is not None and bool(w.exact.any()):
-            n = int((gd[w.exact] != once[w.exact]).sum())
-            if n:
-                errs.append(f"{what}: {n} of the {int(w.exact.sum())} elements that must be exact are not")
+        wo, e = check_want(f"{case.id} {label}", g, w)
+        worst, errs = max(worst, wo), errs + e
     return worst, errs
 
 
