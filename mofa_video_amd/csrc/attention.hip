@@ -1,4 +1,4 @@
-// Attention kernels for gfx950 (head_dim 64).
+// Attention kernels for gfx950 (head_dim 64 or 128).
 //
 // mofa_attn_spatial_f16: flash-style self-attention over the S = h*w tokens of one frame.
 //   One workgroup = 4 waves = 128 (or 256: two 32-query blocks per wave) query rows of one (frame, head); K and V
@@ -17,6 +17,9 @@
 //   key tiles of K and V in the wave's LDS, one 32-query block at a time with all of its score tiles in registers.
 //   mofa_attn_temporal_long_masked_f16: its form for frame-sharded clips (Tq <= T query frames, a key mask);
 //   mofa_attn_temporal_long_local_f16: its form under a per-query rule (a band round the query plus the first frames).
+//   One body (attn_temporal_long_body.inc) included by the three kernels, one launcher, one dispatch, one argument check.
+//
+// mofa_transpose_v_f16, mofa_softmax_rows_f16: the two helpers of the VAE mid-block attention (scores materialised by implicit GEMMs).
 
 #include "common.h"
 
@@ -593,380 +596,135 @@ extern "C" int mofa_attn_temporal_f16(const void* q, const void* k, const void* 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Long temporal attention: 33 .. 128 frames per clip (any 1 <= T <= 128), self-attention only (Tq == T, no key mask).
-// The fragment algebra of attn_temporal_kernel repeated over KT = ceil(T / 32) key tiles and KT query blocks, one wave per
-// sequence.  The wave stages ALL 32 KT key rows of K and V in its own LDS region once (K and V leave HBM once per
-// sequence), then runs one query block after the other: the KT score tiles of a block stay in registers (<= 64 fp32), so
-// the maximum, exp2 and the sum are taken across the tiles directly -- no online-softmax rescale -- and O^T accumulates
-// over the tiles.  Key rows >= T are never read (their LDS rows are zero, their scores -1e30), query rows >= T are never
-// loaded or stored.  LDS per wave: 32 KT (2 D + 40) halves = 10.5 KT KB (D = 64) / 18.5 KT KB (D = 128); dynamic, the
-// D = 128, KT = 4 instantiation (74 KB) needs the opt-in beyond 64 KB.
+// Long temporal attention: 1 <= T <= 128 key frames per clip.  ONE body, attn_temporal_long_body.inc, included by three kernels
+// that differ only in the five rule macros they define for it (the .inc names them and says what is shared):
+//   attn_temporal_long_kernel         self-attention, keys < T
+//   attn_temporal_long_masked_kernel  frame-sharded clips: Tq <= T query frames against T key SLOTS under a 128-bit mask
+//   attn_temporal_long_local_kernel   self-attention under a per-query rule: a band round the query + the first frames
+// The body is shared as TEXT, not as an always-inlined function taking a rule object: with the body in a __device__ function
+// behind one-line __global__ wrappers the compiler no longer keeps the Q-fragment arrays as one wide value -- the dense kernel's
+// own text moved into such a function, nothing else changed, shows it -- and the D = 128 instantiations ran 0.4-1.1 % slower
+// than the three copies.  Included, each kernel compiles to the instructions of its former copy.
 // ---------------------------------------------------------------------------------------------------
+#define TL_SLOT(r) (((r) & 3) + 8 * ((r) >> 2))                    // key of score r inside its lane half's 16
+
+// Dense: key rows >= T are neither loaded nor seen, and KT = ceil(T / 32), so only the last tile reaches beyond T: the test folds
+// away at compile time in every other tile.  No words.
 template <int D, int KT, int WPB>
 __global__ __launch_bounds__(64 * WPB) void attn_temporal_long_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
                                                                       const f16* __restrict__ v, f16* __restrict__ out,
                                                                       long long nseq, int T, int HW, int heads, int ld,
                                                                       int ldkv, int ldo, float scale) {
-    constexpr int DC = D / 8;       // 16-byte chunks per row
-    constexpr int KK = D / 16;      // MFMA k-steps of S^T
-    constexpr int DB = D / 32;      // 32-wide output d-blocks
-    constexpr int KSTR = D + 8;     // K row stride in halves (conflict-free ds_read_b128)
-    constexpr int VSTR = D + 32;    // V row stride in halves (see lds_read_tr4)
-    constexpr int ROWS = 32 * KT;   // staged key rows
-    constexpr int RPI = 64 / DC;    // key rows one wave-wide pass of 16-byte chunks covers (8 / 4)
-    constexpr int UB = 4;           // passes in flight: 2 UB 16-byte loads per lane before the first LDS store
-    extern __shared__ __attribute__((aligned(16))) char smem_tl[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long seq = (long long)blockIdx.x * WPB + wave;
-    if (seq >= nseq) return;                                       // (no workgroup barrier below: LDS regions are per wave)
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int head = (int)(seq % heads);
-    const long long bp = seq / heads;
-    const int p = (int)(bp % HW);
-    const int b = (int)(bp / HW);
-    const size_t base = ((size_t)b * T * HW + p);                  // token row of frame 0 (q, k, v and out alike)
-    f16* wK = (f16*)smem_tl + (size_t)wave * (ROWS * (KSTR + VSTR));
-    f16* wV = wK + ROWS * KSTR;
-    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-
-    // Q fragments of query block 0 (B operand of S^T): lane (query l31, half lh) holds Q[q][16 kk + 8 lh .. + 8)
-    f16x8 qf[KK];
-    {
-        const f16* qp = q + (base + (size_t)(l31 < T ? l31 : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) qf[kk] = l31 < T ? *(const f16x8*)(qp + kk * 16) : zero8;
-    }
-    // ---- K and V rows of the T frames, UB passes at a time; rows >= T are written as zero and never read (a key beyond T
-    //      has probability exactly 0, but 0 * NaN from never-written LDS would not be) ----
-    {
-        const int r0 = lane / DC, cc = lane % DC;
-#pragma unroll 1
-        for (int t0 = 0; t0 < ROWS; t0 += UB * RPI) {
-            f16x8 gk[UB], gv[UB];
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                const int t = t0 + u * RPI + r0;
-                gk[u] = zero8; gv[u] = zero8;
-                if (t < T) {
-                    const size_t off = (base + (size_t)t * HW) * ldkv + head * D + cc * 8;
-                    gk[u] = *(const f16x8*)(k + off);
-                    gv[u] = *(const f16x8*)(v + off);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                const int t = t0 + u * RPI + r0;
-                *(f16x8*)&wK[t * KSTR + cc * 8] = gk[u];
-                *(f16x8*)&wV[t * VSTR + cc * 8] = gv[u];
-            }
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this wave's LDS writes are in place
-    __builtin_amdgcn_wave_barrier();
-
-    const float c2 = scale * 1.4426950408889634f;
-    const int tr_off = (((lane & 15) >> 2) + 4 * lh) * VSTR + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-#pragma unroll 1
-    for (int q0 = 0; q0 < T; q0 += 32) {
-        // the next block's Q fragments are fetched under this block's arithmetic
-        f16x8 qn[KK];
-        {
-            const int qi = q0 + 32 + l31;
-            const f16* qp = q + (base + (size_t)(qi < T ? qi : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) qn[kk] = qi < T ? *(const f16x8*)(qp + kk * 16) : zero8;
-        }
-        // ---- S^T tiles: s[kt][r] = score(key = 32 kt + (r & 3) + 8 (r >> 2) + 4 lh, query = q0 + l31) ----
-        f32x16 s[KT];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
-            const f16* kp = wK + (kt * 32 + l31) * KSTR + lh * 8;
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) {
-                const f16x8 kf = *(const f16x8*)(kp + kk * 16);
-                s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], s[kt], 0, 0, 0);
-            }
-        }
-        float mx = -1e30f;
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if (kt == KT - 1) {                                 // (KT = ceil(T / 32): only the last tile reaches beyond T)
-                    const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (key >= T) s[kt][r] = -1e30f;
-                }
-                mx = fmaxf(mx, s[kt][r]);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mc = mx * c2;
-        float sum = 0.f;
-        f16x8 pf[KT][2];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pr = __builtin_amdgcn_exp2f(fmaf(s[kt][r], c2, -mc));   // keys beyond T: exp2(-huge) = 0
-                sum += pr;
-                pf[kt][r >> 3][r & 7] = (f16)pr;
-            }
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = 1.0f / sum;
-
-        // ---- O^T[d][q] += V^T[d][key] P^T[key][q]; k-slot (8 lh + jj) of MFMA (kt, u) = key
-        //      32 kt + 16 u + 4 lh + (jj & 3) + 8 (jj >> 2), identical for both operands ----
-        f32x16 o[DB];
-#pragma unroll
-        for (int db = 0; db < DB; ++db) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
-            const f16* vp = wV + tr_off + db * 32;
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const f16x4 lo = lds_read_tr4(vp + (kt * 32 + u * 16) * VSTR), hi = lds_read_tr4(vp + (kt * 32 + u * 16 + 8) * VSTR);
-                    const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[kt][u], o[db], 0, 0, 0);
-                }
-        }
-        if (q0 + l31 < T) {
-            f16* op = out + (base + (size_t)(q0 + l31) * HW) * ldo + head * D;
-#pragma unroll
-            for (int db = 0; db < DB; ++db)
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    f16x4 w;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) w[e] = (f16)(o[db][4 * qd + e] * inv);
-                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;
-                }
-        }
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
-    }
+#define TL_TQ T
+#define TL_STAGE_WORD(t0)
+#define TL_STAGED(t) ((t) < T)
+#define TL_WORDS(q0)
+#define TL_HIDDEN(kt, r) ((kt) == KT - 1 && (kt) * 32 + TL_SLOT(r) + 4 * lh >= T)
+#include "attn_temporal_long_body.inc"
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Long temporal attention of frame-sharded clips: attn_temporal_long_kernel with Tq <= T query frames (rows of q / out, clip
-// stride Tq*HW) against T <= 128 key slots of the gathered K|V buffer (rows of k / v, clip stride T*HW) under a 128-bit key
-// mask -- four wave-uniform kernel arguments m0 .. m3, bit j % 32 of word j / 32 = slot j exists; the host clears the bits at
-// and above T, so the kernel tests the mask alone.  The same fragment algebra, staging and LDS layout; a query's arithmetic
-// is that of the self-attention kernel (bit-identical with every slot live).  A dead slot is never read (neither K nor V: the
-// padding slots of the gathered buffer may hold NaN), its LDS rows are zero and its score is -1e30, tested in EVERY tile;
-// query rows >= Tq are neither loaded nor stored and the query loop runs ceil(Tq / 32) blocks.  A kernel of its own, not a
-// template flag on the one above: sharing the body moved that kernel's register allocation (D = 64: KT = 2 124 -> 126 VGPRs,
-// KT = 4 40 -> 50 AGPRs).
-// ---------------------------------------------------------------------------------------------------
+// Masked: four wave-uniform words m0 .. m3, bit j % 32 of word j / 32 = key slot j exists; the host clears the bits at and above
+// T, so the mask alone is tested, in EVERY tile (a dead slot can lie anywhere).  A dead slot is never read, neither K nor V: the
+// padding slots of the gathered buffer may hold NaN.  The rows of one staging iteration lie in one mask word (UB * RPI divides
+// 32), picked per iteration.  The words as a lane half sees them: q0 >> 20 is 0 (Tq <= 128); it keeps the 16 KT bit tests inside
+// the query loop -- hoisted, their lane masks take 32 KT SGPRs and spill at KT >= 3.
 template <int D, int KT, int WPB>
 __global__ __launch_bounds__(64 * WPB) void attn_temporal_long_masked_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
                                                                              const f16* __restrict__ v, f16* __restrict__ out,
                                                                              long long nseq, int Tq, int T, int HW, int heads,
                                                                              int ld, int ldkv, int ldo, float scale, unsigned m0,
                                                                              unsigned m1, unsigned m2, unsigned m3) {
-    constexpr int DC = D / 8;       // 16-byte chunks per row
-    constexpr int KK = D / 16;      // MFMA k-steps of S^T
-    constexpr int DB = D / 32;      // 32-wide output d-blocks
-    constexpr int KSTR = D + 8;     // K row stride in halves (conflict-free ds_read_b128)
-    constexpr int VSTR = D + 32;    // V row stride in halves (see lds_read_tr4)
-    constexpr int ROWS = 32 * KT;   // staged key rows
-    constexpr int RPI = 64 / DC;    // key rows one wave-wide pass of 16-byte chunks covers (8 / 4)
-    constexpr int UB = 4;           // passes in flight: 2 UB 16-byte loads per lane before the first LDS store
-    extern __shared__ __attribute__((aligned(16))) char smem_tl[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long seq = (long long)blockIdx.x * WPB + wave;
-    if (seq >= nseq) return;                                       // (no workgroup barrier below: LDS regions are per wave)
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int head = (int)(seq % heads);
-    const long long bp = seq / heads;
-    const int p = (int)(bp % HW);
-    const int b = (int)(bp / HW);
-    const size_t base = ((size_t)b * T * HW + p);                  // k / v token row of frame 0
-    const size_t qbase = ((size_t)b * Tq * HW + p);                // q / out token row of frame 0
-    f16* wK = (f16*)smem_tl + (size_t)wave * (ROWS * (KSTR + VSTR));
-    f16* wV = wK + ROWS * KSTR;
-    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-
-    // Q fragments of query block 0 (B operand of S^T): lane (query l31, half lh) holds Q[q][16 kk + 8 lh .. + 8)
-    f16x8 qf[KK];
-    {
-        const f16* qp = q + (qbase + (size_t)(l31 < Tq ? l31 : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) qf[kk] = l31 < Tq ? *(const f16x8*)(qp + kk * 16) : zero8;
-    }
-    // ---- K and V rows of the live slots, UB passes at a time; dead slots and rows >= T are written as zero and never read
-    //      (their probability is exactly 0, but 0 * NaN from never-written LDS would not be) ----
-    {
-        const int r0 = lane / DC, cc = lane % DC;
-#pragma unroll 1
-        for (int t0 = 0; t0 < ROWS; t0 += UB * RPI) {
-            // UB * RPI divides 32: the rows of one iteration lie in one mask word (wave-uniform; bits >= T are clear)
-            const unsigned mw = (t0 >> 5) == 0 ? m0 : (t0 >> 5) == 1 ? m1 : (t0 >> 5) == 2 ? m2 : m3;
-            f16x8 gk[UB], gv[UB];
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                const int t = t0 + u * RPI + r0;
-                gk[u] = zero8; gv[u] = zero8;
-                if ((mw >> (t & 31)) & 1u) {
-                    const size_t off = (base + (size_t)t * HW) * ldkv + head * D + cc * 8;
-                    gk[u] = *(const f16x8*)(k + off);
-                    gv[u] = *(const f16x8*)(v + off);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                const int t = t0 + u * RPI + r0;
-                *(f16x8*)&wK[t * KSTR + cc * 8] = gk[u];
-                *(f16x8*)&wV[t * VSTR + cc * 8] = gv[u];
-            }
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this wave's LDS writes are in place
-    __builtin_amdgcn_wave_barrier();
-
-    const float c2 = scale * 1.4426950408889634f;
-    const int tr_off = (((lane & 15) >> 2) + 4 * lh) * VSTR + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-#pragma unroll 1
-    for (int q0 = 0; q0 < Tq; q0 += 32) {
-        // the next block's Q fragments are fetched under this block's arithmetic
-        f16x8 qn[KK];
-        {
-            const int qi = q0 + 32 + l31;
-            const f16* qp = q + (qbase + (size_t)(qi < Tq ? qi : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) qn[kk] = qi < Tq ? *(const f16x8*)(qp + kk * 16) : zero8;
-        }
-        // the mask words as this lane half sees them: bit (r & 3) + 8 (r >> 2) of ml[kt] = the key slot of score s[kt][r].
-        // q0 >> 20 is 0 (Tq <= 128); it keeps the 16 KT bit tests inside the loop -- hoisted, their lane masks take 32 KT
-        // SGPRs and spill at KT >= 3
-        unsigned ml[KT];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-            ml[kt] = ((kt == 0 ? m0 : kt == 1 ? m1 : kt == 2 ? m2 : m3) >> (4 * lh)) | (unsigned)(q0 >> 20);
-        // ---- S^T tiles: s[kt][r] = score(key = 32 kt + (r & 3) + 8 (r >> 2) + 4 lh, query = q0 + l31) ----
-        f32x16 s[KT];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
-            const f16* kp = wK + (kt * 32 + l31) * KSTR + lh * 8;
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) {
-                const f16x8 kf = *(const f16x8*)(kp + kk * 16);
-                s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], s[kt], 0, 0, 0);
-            }
-        }
-        float mx = -1e30f;
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                // every tile: a dead slot can lie anywhere (slots >= T are dead: the host clears their bits)
-                if (!(ml[kt] & (1u << ((r & 3) + 8 * (r >> 2))))) s[kt][r] = -1e30f;
-                mx = fmaxf(mx, s[kt][r]);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mc = mx * c2;
-        float sum = 0.f;
-        f16x8 pf[KT][2];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pr = __builtin_amdgcn_exp2f(fmaf(s[kt][r], c2, -mc));   // dead slots: exp2(-huge) = 0    
-                sum += pr;
-                pf[kt][r >> 3][r & 7] = (f16)pr;
-            }
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = 1.0f / sum;
-
-        // ---- O^T[d][q] += V^T[d][key] P^T[key][q]; k-slot (8 lh + jj) of MFMA (kt, u) = key
-        //      32 kt + 16 u + 4 lh + (jj & 3) + 8 (jj >> 2), identical for both operands ----
-        f32x16 o[DB];
-#pragma unroll
-        for (int db = 0; db < DB; ++db) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
-            const f16* vp = wV + tr_off + db * 32;
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const f16x4 lo = lds_read_tr4(vp + (kt * 32 + u * 16) * VSTR), hi = lds_read_tr4(vp + (kt * 32 + u * 16 + 8) * VSTR);
-                    const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[kt][u], o[db], 0, 0, 0);
-                }
-        }
-        if (q0 + l31 < Tq) {
-            f16* op = out + (qbase + (size_t)(q0 + l31) * HW) * ldo + head * D;
-#pragma unroll
-            for (int db = 0; db < DB; ++db)
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    f16x4 w;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) w[e] = (f16)(o[db][4 * qd + e] * inv);
-                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;
-                }
-        }
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
-    }
+#define TL_MASK_WORD(w) ((w) == 0 ? m0 : (w) == 1 ? m1 : (w) == 2 ? m2 : m3)
+#define TL_TQ Tq
+#define TL_STAGE_WORD(t0) const unsigned mw = TL_MASK_WORD((t0) >> 5);
+#define TL_STAGED(t) ((mw >> ((t) & 31)) & 1u)
+#define TL_WORDS(q0)                    \
+    unsigned ml[KT];                    \
+    _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) ml[kt] = (TL_MASK_WORD(kt) >> (4 * lh)) | (unsigned)((q0) >> 20);
+#define TL_HIDDEN(kt, r) (!(ml[kt] & (1u << TL_SLOT(r))))
+#include "attn_temporal_long_body.inc"
+#undef TL_MASK_WORD
 }
 
+// Local: query frame i sees key frame j iff j < anchor or |i - j| <= radius (every query sees itself, so no row is empty); the
+// host passes radius <= 127 and 0 <= anchor <= T.  All T frames are staged (other queries of the sequence need them), so K and V
+// of the clip's frames must be finite: an invisible frame IS read and multiplied by its zero probability.  The rule reaches a
+// lane as KT words built per query block and tested like the masked kernel's, in every tile: three VALU instructions per score,
+// 1-7 % over the dense kernel's time.  The band's keys lo .. hi lie inside [0, T) and anchor <= T, so keys >= T are invisible;
+// query rows >= T are not stored and take the band of row T - 1.  below(n) = the n lowest bits, n clamped to 0 .. 32.
+template <int D, int KT, int WPB>
+__global__ __launch_bounds__(64 * WPB) void attn_temporal_long_local_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                            const f16* __restrict__ v, f16* __restrict__ out,
+                                                                            long long nseq, int T, int HW, int heads, int ld,
+                                                                            int ldkv, int ldo, float scale, int radius,
+                                                                            int anchor) {
+#define TL_TQ T
+#define TL_STAGE_WORD(t0)
+#define TL_STAGED(t) ((t) < T)
+#define TL_WORDS(q0)                                                                                                \
+    const int qi = min((q0) + l31, T - 1);                                                                          \
+    const int lo = max(qi - radius, 0), hi1 = min(qi + radius, T - 1) + 1;                                          \
+    unsigned ml[KT];                                                                                                \
+    _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) {                                                             \
+        const auto below = [](int n) { return (unsigned)((1ull << min(max(n, 0), 32)) - 1ull); };                   \
+        ml[kt] = (below(anchor - 32 * kt) | (below(hi1 - 32 * kt) & ~below(lo - 32 * kt))) >> (4 * lh);             \
+    }
+#define TL_HIDDEN(kt, r) (!(ml[kt] & (1u << TL_SLOT(r))))
+#include "attn_temporal_long_body.inc"
+}
+#undef TL_SLOT
+
 // waves per workgroup: as many as keep a workgroup's LDS at or below 42 KB (D = 64) / 37 KB (D = 128), at least one
-template <int D, int KT>
+template <int D_, int KT_>
 struct TemporalLongGeom {
+    static constexpr int D = D_, KT = KT_;
     static constexpr int WPB = D == 64 ? (KT == 1 ? 4 : KT == 2 ? 2 : 1) : (KT == 1 ? 2 : 1);
     static constexpr int LDS = WPB * 32 * KT * (2 * D + 40) * 2;
 };
 
-template <int D, int KT>
-static int launch_attn_temporal_long(const void* q, const void* k, const void* v, void* out, long long nseq, int T, int HW,
-                                     int heads, int ld, int ldkv, int ldo, float scale, hipStream_t st) {
-    constexpr int WPB = TemporalLongGeom<D, KT>::WPB, LDS = TemporalLongGeom<D, KT>::LDS;
-    const long long nwg = (nseq + WPB - 1) / WPB;
+// one launcher for the three forms: Kernel is a template argument, so the LDS opt-in (per function and per device) is taken
+// once per kernel instantiation
+template <class G, auto Kernel, class... Args>
+static int launch_temporal_long(long long nseq, hipStream_t st, Args... args) {
+    const long long nwg = (nseq + G::WPB - 1) / G::WPB;
     if (nwg > 0x7fffffffLL) return MOFA_EINVAL;
     static LaunchSetup setup;
-    if (setup.cus([](int) { return mofa_lds_optin((const void*)attn_temporal_long_kernel<D, KT, WPB>, LDS); }) == 0) return MOFA_ELAUNCH;
-    hipLaunchKernelGGL((attn_temporal_long_kernel<D, KT, WPB>), dim3((unsigned)nwg), dim3(64 * WPB), LDS, st, (const f16*)q,
-                       (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale);
+    if (setup.cus([](int) { return mofa_lds_optin((const void*)Kernel, G::LDS); }) == 0) return MOFA_ELAUNCH;
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)nwg), dim3(64 * G::WPB), G::LDS, st, args...);
     MOFA_CHECK_LAUNCH();
     return MOFA_OK;
 }
 
-template <int D, int KT>
-static int launch_attn_temporal_long_masked(const void* q, const void* k, const void* v, void* out, long long nseq, int Tq, int T,
-                                            int HW, int heads, int ld, int ldkv, int ldo, float scale, const uint32_t* m,
-                                            hipStream_t st) {
-    constexpr int WPB = TemporalLongGeom<D, KT>::WPB, LDS = TemporalLongGeom<D, KT>::LDS;
-    const long long nwg = (nseq + WPB - 1) / WPB;
-    if (nwg > 0x7fffffffLL) return MOFA_EINVAL;
-    static LaunchSetup setup;
-    if (setup.cus([](int) { return mofa_lds_optin((const void*)attn_temporal_long_masked_kernel<D, KT, WPB>, LDS); }) == 0) return MOFA_ELAUNCH;
-    hipLaunchKernelGGL((attn_temporal_long_masked_kernel<D, KT, WPB>), dim3((unsigned)nwg), dim3(64 * WPB), LDS, st, (const f16*)q,
-                       (const f16*)k, (const f16*)v, (f16*)out, nseq, Tq, T, HW, heads, ld, ldkv, ldo, scale, m[0], m[1], m[2], m[3]);
-    MOFA_CHECK_LAUNCH();
-    return MOFA_OK;
+// the (head dim, key tiles) instantiation of a call: f(TemporalLongGeom<D, KT>{})
+template <class F>
+static int temporal_long_dispatch(int head_dim, int T, F&& f) {
+    const int kt = (T + 31) / 32;
+#define MOFA_TL_CASE(D_, KT_) \
+    if (head_dim == D_ && kt == KT_) return f(TemporalLongGeom<D_, KT_>{});
+    MOFA_TL_CASE(64, 1) MOFA_TL_CASE(64, 2) MOFA_TL_CASE(64, 3) MOFA_TL_CASE(64, 4)
+    MOFA_TL_CASE(128, 1) MOFA_TL_CASE(128, 2) MOFA_TL_CASE(128, 3) MOFA_TL_CASE(128, 4)
+#undef MOFA_TL_CASE
+    return MOFA_EINVAL;
+}
+
+// what the three entry points ask of their common arguments
+static bool temporal_long_args_ok(const void* q, const void* k, const void* v, const void* out, int nclips, int T, int HW, int heads,
+                                  int head_dim, int ld, int ldkv, int ldo) {
+    if (!q || !k || !v || !out || nclips <= 0 || T < 1 || T > 128 || HW <= 0 || heads <= 0) return false;
+    if (head_dim != 64 && head_dim != 128) return false;
+    return ld > 0 && ldkv > 0 && ldo > 0 && ld % 8 == 0 && ldkv % 8 == 0 && ldo % 8 == 0;
 }
 
 extern "C" int mofa_attn_temporal_long_f16(const void* q, const void* k, const void* v, void* out, int nclips, int T, int HW,
                                            int heads, int head_dim, int ld, int ldkv, int ldo, float scale,
                                            mofa_stream_t stream) {
-    if (!q || !k || !v || !out || nclips <= 0 || T < 1 || T > 128 || HW <= 0 || heads <= 0) return MOFA_EINVAL;
-    if (head_dim != 64 && head_dim != 128) return MOFA_EINVAL;
-    if (ld <= 0 || ldkv <= 0 || ldo <= 0 || ld % 8 != 0 || ldkv % 8 != 0 || ldo % 8 != 0) return MOFA_EINVAL;
+    if (!temporal_long_args_ok(q, k, v, out, nclips, T, HW, heads, head_dim, ld, ldkv, ldo)) return MOFA_EINVAL;
     const long long nseq = (long long)nclips * HW * heads;
-    const int kt = (T + 31) / 32;
-    hipStream_t st = (hipStream_t)stream;
-#define MOFA_TL_CASE(D_, KT_) \
-    if (head_dim == D_ && kt == KT_) return launch_attn_temporal_long<D_, KT_>(q, k, v, out, nseq, T, HW, heads, ld, ldkv, ldo, scale, st);
-    MOFA_TL_CASE(64, 1) MOFA_TL_CASE(64, 2) MOFA_TL_CASE(64, 3) MOFA_TL_CASE(64, 4)
-    MOFA_TL_CASE(128, 1) MOFA_TL_CASE(128, 2) MOFA_TL_CASE(128, 3) MOFA_TL_CASE(128, 4)
-#undef MOFA_TL_CASE
-    return MOFA_EINVAL;
+    return temporal_long_dispatch(head_dim, T, [&](auto g) {
+        using G = decltype(g);
+        return launch_temporal_long<G, attn_temporal_long_kernel<G::D, G::KT, G::WPB>>(
+            nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale);
+    });
 }
 
 // key_mask: host memory, four words, bit j % 32 of word j / 32 = key slot j exists; NULL = every slot below T.  Bits at and
@@ -974,9 +732,7 @@ extern "C" int mofa_attn_temporal_long_f16(const void* q, const void* k, const v
 extern "C" int mofa_attn_temporal_long_masked_f16(const void* q, const void* k, const void* v, void* out, int nclips, int Tq,
                                                   int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo, float scale,
                                                   const uint32_t* key_mask, mofa_stream_t stream) {
-    if (!q || !k || !v || !out || nclips <= 0 || T < 1 || T > 128 || Tq < 1 || Tq > T || HW <= 0 || heads <= 0) return MOFA_EINVAL;
-    if (head_dim != 64 && head_dim != 128) return MOFA_EINVAL;
-    if (ld <= 0 || ldkv <= 0 || ldo <= 0 || ld % 8 != 0 || ldkv % 8 != 0 || ldo % 8 != 0) return MOFA_EINVAL;
+    if (!temporal_long_args_ok(q, k, v, out, nclips, T, HW, heads, head_dim, ld, ldkv, ldo) || Tq < 1 || Tq > T) return MOFA_EINVAL;
     uint32_t m[4];
     for (int w = 0; w < 4; ++w) {
         const int n = T - 32 * w;                                   // slots of this word below T
@@ -985,201 +741,12 @@ extern "C" int mofa_attn_temporal_long_masked_f16(const void* q, const void* k, 
     }
     if ((m[0] | m[1] | m[2] | m[3]) == 0) return MOFA_EINVAL;
     const long long nseq = (long long)nclips * HW * heads;
-    const int kt = (T + 31) / 32;
-    hipStream_t st = (hipStream_t)stream;
-#define MOFA_TL_CASE(D_, KT_) \
-    if (head_dim == D_ && kt == KT_) \
-        return launch_attn_temporal_long_masked<D_, KT_>(q, k, v, out, nseq, Tq, T, HW, heads, ld, ldkv, ldo, scale, m, st);
-    MOFA_TL_CASE(64, 1) MOFA_TL_CASE(64, 2) MOFA_TL_CASE(64, 3) MOFA_TL_CASE(64, 4)
-    MOFA_TL_CASE(128, 1) MOFA_TL_CASE(128, 2) MOFA_TL_CASE(128, 3) MOFA_TL_CASE(128, 4)
-#undef MOFA_TL_CASE
-    return MOFA_EINVAL;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Local long temporal attention: attn_temporal_long_kernel under a per-QUERY visibility rule given by two wave-uniform
-// integers -- query frame i sees key frame j iff j < anchor or |i - j| <= radius (a band around the query plus the first
-// `anchor` frames; every query sees itself, so no row is empty).  The same staging, LDS layout and fragment algebra: all T
-// frames of K and V are staged (other queries of the sequence need them), a lane owns one query and all KT score tiles, and
-// an invisible score is set to -1e30 before the row maximum, in EVERY tile, together with the key >= T test; softmax and P V
-// are those of the dense kernel operation for operation, so an invisible key has probability exactly 0 and a rule that hides
-// nothing gives the dense kernel's bits.  The rule reaches a lane as KT words built per query block (bit = the key of a score is
-// visible), tested like the masked kernel's words: three VALU instructions per score, 1-7 % over the dense kernel's time.  No
-// key tile is skipped: wave-uniform branches round the dead tiles of a query block cut the block's straight-line code, in which
-// MFMAs and softmax arithmetic overlap, into pieces, and ran 1.25-1.46 x the dense time at KT >= 3.
-// K and V of the clip's frames must be finite: an invisible frame IS read and multiplied by its zero probability.
-// The host passes radius <= 127 and 0 <= anchor <= T.  A kernel of its own for the reason given above the masked kernel.
-// ---------------------------------------------------------------------------------------------------
-template <int D, int KT, int WPB>
-__global__ __launch_bounds__(64 * WPB) void attn_temporal_long_local_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
-                                                                            const f16* __restrict__ v, f16* __restrict__ out,
-                                                                            long long nseq, int T, int HW, int heads, int ld,
-                                                                            int ldkv, int ldo, float scale, int radius,
-                                                                            int anchor) {
-    constexpr int DC = D / 8;       // 16-byte chunks per row
-    constexpr int KK = D / 16;      // MFMA k-steps of S^T
-    constexpr int DB = D / 32;      // 32-wide output d-blocks
-    constexpr int KSTR = D + 8;     // K row stride in halves (conflict-free ds_read_b128)
-    constexpr int VSTR = D + 32;    // V row stride in halves (see lds_read_tr4)
-    constexpr int ROWS = 32 * KT;   // staged key rows
-    constexpr int RPI = 64 / DC;    // key rows one wave-wide pass of 16-byte chunks covers (8 / 4)
-    constexpr int UB = 4;           // passes in flight: 2 UB 16-byte loads per lane before the first LDS store
-    extern __shared__ __attribute__((aligned(16))) char smem_tl[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long seq = (long long)blockIdx.x * WPB + wave;
-    if (seq >= nseq) return;                                       // (no workgroup barrier below: LDS regions are per wave)
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int head = (int)(seq % heads);
-    const long long bp = seq / heads;
-    const int p = (int)(bp % HW);
-    const int b = (int)(bp / HW);
-    const size_t base = ((size_t)b * T * HW + p);                  // token row of frame 0 (q, k, v and out alike)
-    f16* wK = (f16*)smem_tl + (size_t)wave * (ROWS * (KSTR + VSTR));
-    f16* wV = wK + ROWS * KSTR;
-    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-
-    // Q fragments of query block 0 (B operand of S^T): lane (query l31, half lh) holds Q[q][16 kk + 8 lh .. + 8)
-    f16x8 qf[KK];
-    {
-        const f16* qp = q + (base + (size_t)(l31 < T ? l31 : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) qf[kk] = l31 < T ? *(const f16x8*)(qp + kk * 16) : zero8;
-    }
-    // ---- K and V rows of the T frames, UB passes at a time; rows >= T are written as zero and never read (a key beyond T
-    //      has probability exactly 0, but 0 * NaN from never-written LDS would not be) ----
-    {
-        const int r0 = lane / DC, cc = lane % DC;
-#pragma unroll 1
-        for (int t0 = 0; t0 < ROWS; t0 += UB * RPI) {
-            f16x8 gk[UB], gv[UB];
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                const int t = t0 + u * RPI + r0;
-                gk[u] = zero8; gv[u] = zero8;
-                if (t < T) {
-                    const size_t off = (base + (size_t)t * HW) * ldkv + head * D + cc * 8;
-                    gk[u] = *(const f16x8*)(k + off);
-                    gv[u] = *(const f16x8*)(v + off);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                const int t = t0 + u * RPI + r0;
-                *(f16x8*)&wK[t * KSTR + cc * 8] = gk[u];
-                *(f16x8*)&wV[t * VSTR + cc * 8] = gv[u];
-            }
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this wave's LDS writes are in place
-    __builtin_amdgcn_wave_barrier();
-
-    const float c2 = scale * 1.4426950408889634f;
-    const int tr_off = (((lane & 15) >> 2) + 4 * lh) * VSTR + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-#pragma unroll 1
-    for (int q0 = 0; q0 < T; q0 += 32) {
-        // the next block's Q fragments are fetched under this block's arithmetic
-        f16x8 qn[KK];
-        {
-            const int qi = q0 + 32 + l31;
-            const f16* qp = q + (base + (size_t)(qi < T ? qi : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) qn[kk] = qi < T ? *(const f16x8*)(qp + kk * 16) : zero8;
-        }
-        // the visibility of this lane's query as KT words: bit (r & 3) + 8 (r >> 2) of ml[kt] = the key of score s[kt][r] is
-        // visible.  Keys lo .. hi of the band lie inside [0, T) and anchor <= T, so keys >= T are invisible; query rows >= T are
-        // not stored and take the band of row T - 1.  below(n) = the n lowest bits, n clamped to 0 .. 32
-        const int qi = min(q0 + l31, T - 1);
-        const int lo = max(qi - radius, 0), hi1 = min(qi + radius, T - 1) + 1;
-        unsigned ml[KT];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt) {
-            const auto below = [](int n) { return (unsigned)((1ull << min(max(n, 0), 32)) - 1ull); };
-            ml[kt] = (below(anchor - 32 * kt) | (below(hi1 - 32 * kt) & ~below(lo - 32 * kt))) >> (4 * lh);
-        }
-        // ---- S^T tiles: s[kt][r] = score(key = 32 kt + (r & 3) + 8 (r >> 2) + 4 lh, query = q0 + l31) ----
-        f32x16 s[KT];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
-            const f16* kp = wK + (kt * 32 + l31) * KSTR + lh * 8;
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) {
-                const f16x8 kf = *(const f16x8*)(kp + kk * 16);
-                s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], s[kt], 0, 0, 0);
-            }
-        }
-        float mx = -1e30f;
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                // every tile: an invisible key can lie anywhere (anchor <= T and hi <= T - 1: keys >= T are invisible)
-                if (!(ml[kt] & (1u << ((r & 3) + 8 * (r >> 2))))) s[kt][r] = -1e30f;
-                mx = fmaxf(mx, s[kt][r]);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mc = mx * c2;
-        float sum = 0.f;
-        f16x8 pf[KT][2];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pr = __builtin_amdgcn_exp2f(fmaf(s[kt][r], c2, -mc));   // invisible keys: exp2(-huge) = 0
-                sum += pr;
-                pf[kt][r >> 3][r & 7] = (f16)pr;
-            }
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = 1.0f / sum;
-
-        // ---- O^T[d][q] += V^T[d][key] P^T[key][q]; k-slot (8 lh + jj) of MFMA (kt, u) = key
-        //      32 kt + 16 u + 4 lh + (jj & 3) + 8 (jj >> 2), identical for both operands ----
-        f32x16 o[DB];
-#pragma unroll
-        for (int db = 0; db < DB; ++db) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
-            const f16* vp = wV + tr_off + db * 32;
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const f16x4 lo = lds_read_tr4(vp + (kt * 32 + u * 16) * VSTR), hi = lds_read_tr4(vp + (kt * 32 + u * 16 + 8) * VSTR);
-                    const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[kt][u], o[db], 0, 0, 0);
-                }
-        }
-        if (q0 + l31 < T) {
-            f16* op = out + (base + (size_t)(q0 + l31) * HW) * ldo + head * D;
-#pragma unroll
-            for (int db = 0; db < DB; ++db)
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    f16x4 w;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) w[e] = (f16)(o[db][4 * qd + e] * inv);
-                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;
-                }
-        }
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
-    }
-}
-
-template <int D, int KT>
-static int launch_attn_temporal_long_local(const void* q, const void* k, const void* v, void* out, long long nseq, int T, int HW,
-                                           int heads, int ld, int ldkv, int ldo, float scale, int radius, int anchor,
-                                           hipStream_t st) {
-    constexpr int WPB = TemporalLongGeom<D, KT>::WPB, LDS = TemporalLongGeom<D, KT>::LDS;
-    const long long nwg = (nseq + WPB - 1) / WPB;
-    if (nwg > 0x7fffffffLL) return MOFA_EINVAL;
-    static LaunchSetup setup;
-    if (setup.cus([](int) { return mofa_lds_optin((const void*)attn_temporal_long_local_kernel<D, KT, WPB>, LDS); }) == 0) return MOFA_ELAUNCH;
-    hipLaunchKernelGGL((attn_temporal_long_local_kernel<D, KT, WPB>), dim3((unsigned)nwg), dim3(64 * WPB), LDS, st, (const f16*)q,
-                       (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale, radius, anchor);
-    MOFA_CHECK_LAUNCH();
-    return MOFA_OK;
+    return temporal_long_dispatch(head_dim, T, [&](auto g) {
+        using G = decltype(g);
+        return launch_temporal_long<G, attn_temporal_long_masked_kernel<G::D, G::KT, G::WPB>>(
+            nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, Tq, T, HW, heads, ld, ldkv, ldo, scale,
+            m[0], m[1], m[2], m[3]);
+    });
 }
 
 // query frame i sees key frame j iff j < anchor or |i - j| <= radius; radius > T - 1 means "all" (clamped here: the kernel adds
@@ -1187,21 +754,16 @@ static int launch_attn_temporal_long_local(const void* q, const void* k, const v
 extern "C" int mofa_attn_temporal_long_local_f16(const void* q, const void* k, const void* v, void* out, int nclips, int T, int HW,
                                                  int heads, int head_dim, int ld, int ldkv, int ldo, float scale, int radius,
                                                  int anchor, mofa_stream_t stream) {
-    if (!q || !k || !v || !out || nclips <= 0 || T < 1 || T > 128 || HW <= 0 || heads <= 0) return MOFA_EINVAL;
-    if (head_dim != 64 && head_dim != 128) return MOFA_EINVAL;
-    if (ld <= 0 || ldkv <= 0 || ldo <= 0 || ld % 8 != 0 || ldkv % 8 != 0 || ldo % 8 != 0) return MOFA_EINVAL;
+    if (!temporal_long_args_ok(q, k, v, out, nclips, T, HW, heads, head_dim, ld, ldkv, ldo)) return MOFA_EINVAL;
     if (radius < 0 || anchor < 0 || anchor > T) return MOFA_EINVAL;
     if (radius > 127) radius = 127;
     const long long nseq = (long long)nclips * HW * heads;
-    const int kt = (T + 31) / 32;
-    hipStream_t st = (hipStream_t)stream;
-#define MOFA_TL_CASE(D_, KT_) \
-    if (head_dim == D_ && kt == KT_) \
-        return launch_attn_temporal_long_local<D_, KT_>(q, k, v, out, nseq, T, HW, heads, ld, ldkv, ldo, scale, radius, anchor, st);
-    MOFA_TL_CASE(64, 1) MOFA_TL_CASE(64, 2) MOFA_TL_CASE(64, 3) MOFA_TL_CASE(64, 4)
-    MOFA_TL_CASE(128, 1) MOFA_TL_CASE(128, 2) MOFA_TL_CASE(128, 3) MOFA_TL_CASE(128, 4)
-#undef MOFA_TL_CASE
-    return MOFA_EINVAL;
+    return temporal_long_dispatch(head_dim, T, [&](auto g) {
+        using G = decltype(g);
+        return launch_temporal_long<G, attn_temporal_long_local_kernel<G::D, G::KT, G::WPB>>(
+            nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale,
+            radius, anchor);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -425,6 +425,18 @@ def attn_spatial(q, k, v, nframes, heads, S, head_dim=64, scale=None, out=None, 
     return out
 
 
+def _attn_temporal_prologue(q, k, v, rows, heads, head_dim, scale, out):
+    """what the temporal entry points share: the library, the default scale, and ``out`` allocated (``rows`` query rows) or marked"""
+    lib = L.load()
+    assert _ld(k) == _ld(v)
+    scale = head_dim ** -0.5 if scale is None else scale
+    if out is None:
+        out = torch.empty((rows, heads * head_dim), dtype=F16, device=q.device)
+    else:
+        _written(out)
+    return lib, scale, out
+
+
 def attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=None, Tq=None, key_mask=None):
     """k/v hold T frames per clip; q holds Tq <= T (Tq < T: frame-sharded clip with all-gathered K/V).  key_mask: bit j =
     key frame j exists (padding frames of uneven shards in the gathered buffer are masked, never read).
@@ -434,13 +446,7 @@ def attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=No
     if T > 32 and (key_mask is not None or Tq != T):
         raise ValueError(f"temporal attention over {T} key frames with a key mask or Tq < T: frame-sharded clips are limited "
                          "to 32 key slots")
-    lib = L.load()
-    assert _ld(k) == _ld(v)
-    scale = head_dim ** -0.5 if scale is None else scale
-    if out is None:
-        out = torch.empty((nclips * Tq * HW, heads * head_dim), dtype=F16, device=q.device)
-    else:
-        _written(out)
+    lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * Tq * HW, heads, head_dim, scale, out)
     if T > 32:
         t0 = TIMER.start() if TIMER is not None else None
         L.check(lib.mofa_attn_temporal_long_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, T, HW, heads, head_dim,
@@ -465,13 +471,7 @@ def attn_temporal_sharded(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None
     if T <= 32:
         return attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=head_dim, scale=scale, out=out, Tq=Tq, key_mask=key_mask)
     Tq = T if Tq is None else Tq
-    lib = L.load()
-    assert _ld(k) == _ld(v)
-    scale = head_dim ** -0.5 if scale is None else scale
-    if out is None:
-        out = torch.empty((nclips * Tq * HW, heads * head_dim), dtype=F16, device=q.device)
-    else:
-        _written(out)
+    lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * Tq * HW, heads, head_dim, scale, out)
     words = None
     if key_mask is not None:
         m = int(key_mask)
@@ -504,13 +504,7 @@ def attn_temporal_local(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, 
     if local is None:
         raise ValueError("local=(radius, anchor) is required; dense temporal attention is attn_temporal")
     radius, anchor = (int(x) for x in local)
-    lib = L.load()
-    assert _ld(k) == _ld(v)
-    scale = head_dim ** -0.5 if scale is None else scale
-    if out is None:
-        out = torch.empty((nclips * T * HW, heads * head_dim), dtype=F16, device=q.device)
-    else:
-        _written(out)
+    lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * T * HW, heads, head_dim, scale, out)
     t0 = TIMER.start() if TIMER is not None else None
     L.check(lib.mofa_attn_temporal_long_local_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, T, HW, heads, head_dim,
                                                   _ld(q), _ld(k), _ld(out), scale, radius, anchor, L.stream_ptr()),

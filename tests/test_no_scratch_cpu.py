@@ -26,7 +26,7 @@ def _usage(src):
         if m:
             name = m.group(1)
             rows[name] = {}
-        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
+        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
         if m and name:
             rows[name][m.group(1).split(" [")[0]] = int(m.group(2))
     return rows
@@ -48,6 +48,27 @@ def test_hot_kernels_use_no_scratch():
                 bad.append((src, name, r))
     assert seen >= 37
     assert not bad, bad
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
+def test_long_temporal_attention_instantiations():
+    """the three long temporal attention kernels include one body (csrc/attn_temporal_long_body.inc): each has exactly the eight instantiations
+    (head dim, key tiles, waves per workgroup) the launcher dispatches to, none with scratch, a VGPR spill or an SGPR spill (the
+    mask's 16 KT bit tests, hoisted out of the query loop, once took 42 SGPRs too many), and each at the occupancy [waves / SIMD]
+    by (head dim, key tiles) that the three separate copies of the body had before they were merged"""
+    occupancy = {(64, 1, 4): 4, (64, 2, 2): 3, (64, 3, 1): 2, (64, 4, 1): 2, (128, 1, 2): 2, (128, 2, 1): 2, (128, 3, 1): 1, (128, 4, 1): 1}
+    usage = _usage("attention.hip")
+    for kernel in ("attn_temporal_long_kernel", "attn_temporal_long_masked_kernel", "attn_temporal_long_local_kernel"):
+        rows = {}
+        for n, r in usage.items():
+            m = re.match(r"_Z\d+" + kernel + r"ILi(\d+)ELi(\d+)ELi(\d+)EE", n)
+            if m:
+                inst = tuple(int(x) for x in m.groups())
+                assert inst not in rows, (kernel, inst)
+                rows[inst] = r
+        assert set(rows) == set(occupancy), (kernel, sorted(rows))
+        for inst, r in rows.items():
+            assert r == {"ScratchSize": 0, "VGPRs Spill": 0, "SGPRs Spill": 0, "Occupancy": occupancy[inst]}, (kernel, inst, r)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")

@@ -2,15 +2,13 @@
 declared, exported, bound and validates its arguments before any device call; ``ops.attn_temporal_sharded`` hands T <= 32 to
 ``ops.attn_temporal`` unchanged; ``FrameParallel(max_key_slots=...)`` and what ``pipeline._check_call`` makes of it; the masked
 case table of tests/attn_long_masked_cases.py through the stand-in of tests/emu_sharded.py, with mutants of the mask handling
-that prove the checks can fail; the sharded temporal block and the whole sharded UNet over gloo at 37 ... 128 frames; and the
-resource report of the new kernel instantiations."""
+that prove the checks can fail; the sharded temporal block and the whole sharded UNet over gloo at 37 ... 128 frames.  (The
+resource report of the kernel's instantiations: tests/test_no_scratch_cpu.py.)"""
 import ctypes
 import inspect
 import os
 import re
-import shutil
 import socket
-import subprocess
 import types
 
 import pytest
@@ -294,32 +292,3 @@ def test_sharded_long_unet_forward_gloo(world, T):
     every rank's noise prediction for its frames against the rows of the unsharded forward at 64 x 64 pixels, under the 2e-3
     that tests/test_parallel_gloo.py::test_sharded_unet_forward_gloo states for this comparison on the stand-ins"""
     mp.spawn(_unet_worker, args=(world, _free_port(), T), nprocs=world, join=True)
-
-
-# ---- resources ----------------------------------------------------------------------------------------------------------------
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
-def test_masked_instantiations_use_no_scratch_and_spill_nothing():
-    """the eight instantiations (head dim 64 / 128 x 1 ... 4 key tiles) from the cross-compiled resource report: no scratch, no
-    VGPR spill and no SGPR spill either (the mask's 16 KT bit tests, hoisted out of the query loop, once took 42 SGPRs too many)"""
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-           os.path.join(ROOT, "mofa_video_amd", "csrc", "attention.hip"), "-o", os.devnull]
-    out = subprocess.run(cmd, capture_output=True, text=True).stderr
-    rows, name = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            rows[name] = {}
-        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill): (\d+)", line)
-        if m and name:
-            rows[name][m.group(1).split(" [")[0]] = int(m.group(2))
-    new = {n: r for n, r in rows.items() if "attn_temporal_long_masked_kernel" in n}
-    tags = sorted(re.search(r"kernelILi(\d+)ELi(\d+)ELi(\d+)E", n).groups() for n in new)
-    assert tags == sorted([("64", "1", "4"), ("64", "2", "2"), ("64", "3", "1"), ("64", "4", "1"),
-                           ("128", "1", "2"), ("128", "2", "1"), ("128", "3", "1"), ("128", "4", "1")]), tags
-    for n, r in new.items():
-        assert r == {"ScratchSize": 0, "VGPRs Spill": 0, "SGPRs Spill": 0}, (n, r)
-    assert sum("attn_temporal_long_kernel" in n for n in rows) == 8
