@@ -206,6 +206,21 @@ int mofa_attn_temporal_long_masked_f16(const void* q, const void* k, const void*
 int mofa_attn_temporal_long_local_f16(const void* q, const void* k, const void* v, void* out,
                                       int nclips, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
                                       float scale, int radius, int anchor, mofa_stream_t stream);
+/* Streaming local temporal self-attention over 1 <= T <= 1024 frames: the rule, the row layout and the scale convention of
+ * mofa_attn_temporal_long_local_f16,
+ *     query frame i sees key frame j  iff  j < anchor  or  |i - j| <= radius
+ * under 0 <= radius <= 32 and 0 <= anchor <= min(T, 32).  A 32-query block then needs frame tile 0 and three band tiles only,
+ * so one wave keeps four 32-frame tile slots in LDS (tile 0 and a ring of three, refilled after each block) whatever T is; K
+ * and V are read from memory once, rows of frames >= T are never read or written.  Precondition: K and V of all T frames are
+ * finite -- an invisible frame of a staged tile is multiplied by its zero probability.  Two equalities hold bit for bit: for
+ * T <= 128 the output is that of mofa_attn_temporal_long_local_f16 under the same (radius, anchor); and for every T, row i of
+ * query block tq = i / 32 is row i % 32 of mofa_attn_temporal_long_masked_f16 called with Tq == T == 128 on the frame tiles
+ * [0, tq - 1, tq, tq + 1] (a slot that is out of range or a second copy of tile 0 dead) under the mask {slots i sees}.
+ * MOFA_EINVAL for everything mofa_attn_temporal_long_f16 refuses, with T > 1024 in place of T > 128, and for radius < 0,
+ * radius > 32, anchor < 0, anchor > 32 or anchor > T -- all checked before any device call. */
+int mofa_attn_temporal_stream_local_f16(const void* q, const void* k, const void* v, void* out,
+                                        int nclips, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
+                                        float scale, int radius, int anchor, mofa_stream_t stream);
 /* in-place row softmax of an fp16 [rows][cols] matrix (VAE mid-block attention, 1 head x 512) */
 int mofa_softmax_rows_f16(void* x, int rows, int cols, int ld, mofa_stream_t stream);
 

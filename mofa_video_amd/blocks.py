@@ -23,6 +23,9 @@ from . import ops
 from .weights import (f32, interleave_geglu, pack_conv3d_t3, pack_conv3x3, pack_ff320, pack_lin320, pack_linear, pad_rows)
 
 BIG = 1 << 30
+# local temporal attention (Ctx.local): clips of up to this many frames go to ops.attn_temporal_local, whose kernel stages the
+# whole clip's keys; longer ones to ops.attn_temporal_local_stream (four key tiles in a ring, radius and anchor <= 32)
+LOCAL_STREAM_ABOVE = 128
 
 
 class Sub:
@@ -471,7 +474,8 @@ class TransformerSpatioTemporal:
             if c.local is None:
                 a = ops.attn_temporal(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim)
             else:
-                a = ops.attn_temporal_local(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim, local=c.local)
+                local = ops.attn_temporal_local if T <= LOCAL_STREAM_ABOVE else ops.attn_temporal_local_stream
+                a = local(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim, local=c.local)
         else:
             # this rank holds T of the clip's T_full frames.  The K|V projection writes this shard's slot of the gather
             # buffer, one all_gather_into_tensor (asynchronous, RCCL's stream) fills the other slots while the Q

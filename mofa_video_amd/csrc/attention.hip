@@ -672,6 +672,216 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_long_local_kernel(cons
 #define TL_HIDDEN(kt, r) (!(ml[kt] & (1u << TL_SLOT(r))))
 #include "attn_temporal_long_body.inc"
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Streaming local temporal attention: the local rule (above) for 1 <= T <= 1024 frames under radius <= 32 and anchor <= 32.  A
+// 32-query block tq = q0 / 32 then sees only frame tile 0 (the anchors) and the frame tiles tq - 1, tq, tq + 1 (the band), so
+// the wave keeps FOUR 32-row tile slots in its LDS region -- the strides and the byte count of the KT = 4 geometry -- however
+// long the clip is:
+//   slot 0       frame tile 0, staged once, for the whole sequence
+//   slots 1 .. 3 a ring: frame tile t >= 1 lives in slot 1 + t % 3
+// and every block computes four register score tiles in the order [tile 0, tq - 1, tq, tq + 1].  The first carries the full
+// rule (anchor and band); a band tile that is out of range (< 0 or >= ceil(T / 32)) or IS tile 0 is hidden as a whole: score
+// -1e30 before the maximum, probability exactly 0.  So every key is counted once and the tiles are visited in ascending frame
+// order: the nonzero terms of the fp32 row sum and of O^T are those of the local kernel (T <= 128) in its order, and exact
+// zeros move neither -- the two kernels agree bit for bit there.  No tile is skipped by a branch (see the body file).
+// Ring: before block 0 tile 1 is staged into slot 2 and slots 1 and 3 are zero-filled (tile 0 never enters the ring: its band
+// copy is hidden); after block tq, tile tq + 2 is staged into the slot tile tq - 1 leaves -- tq + 2 = tq - 1 (mod 3).  The
+// tile's global loads are issued at the top of the block into registers (16 / 32 VGPRs each for K and V) and travel under its
+// arithmetic; its LDS stores follow the block's last LDS read in program order, behind s_waitcnt lgkmcnt(0) and a wave barrier,
+// and one wave's LDS operations execute in order; a second wait and barrier precede the next block's reads.  The refill is
+// unconditional (the last blocks write zeros), so the loop body has no branch.  At three (D = 64) or two (D = 128) waves per CU
+// -- the LDS decides, not the registers -- nothing else hides the load: without the prefetch the kernel ran 1.12-1.22 x its
+// time.  K and V leave HBM once.
+// Every row an MFMA can read is finite at all times: rows of frames >= T are written as zero, the slots of tile -1 (block 0) and
+// of tiles past the last hold zeros or an earlier, finite tile.  Precondition as for the local kernel: K and V of all T frames
+// are finite.  Query rows >= T are neither loaded nor stored.
+// ---------------------------------------------------------------------------------------------------
+// one 32-row tile of K and V in flight between memory and its LDS slot: lane (r0, cc) holds the 16-byte chunk cc of the rows
+// r0, r0 + RPI, ...
+template <int D>
+struct TemporalStreamTile {
+    static constexpr int DC = D / 8, KSTR = D + 8, VSTR = D + 32, RPI = 64 / DC, N = 32 / RPI;
+    f16x8 gk[N], gv[N];
+    // frame rows t_first .. t_first + 32; rows >= T are not read and become zero
+    __device__ __forceinline__ void load(const f16* __restrict__ k, const f16* __restrict__ v, size_t base, int HW, int ldkv, int head,
+                                         int T, int t_first, int lane) {
+        const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+        const int r0 = lane / DC, cc = lane % DC;
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            const int t = t_first + u * RPI + r0;
+            gk[u] = zero8; gv[u] = zero8;
+            if (t < T) {
+                const size_t off = (base + (size_t)t * HW) * ldkv + head * D + cc * 8;
+                gk[u] = *(const f16x8*)(k + off);
+                gv[u] = *(const f16x8*)(v + off);
+            }
+        }
+    }
+    // into the 32-row slot at rk / rv
+    __device__ __forceinline__ void store(f16* rk, f16* rv, int lane) const {
+        const int r0 = lane / DC, cc = lane % DC;
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            const int i = u * RPI + r0;
+            *(f16x8*)&rk[i * KSTR + cc * 8] = gk[u];
+            *(f16x8*)&rv[i * VSTR + cc * 8] = gv[u];
+        }
+    }
+};
+
+template <int D, int WPB>
+__global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_local_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                              const f16* __restrict__ v, f16* __restrict__ out,
+                                                                              long long nseq, int T, int HW, int heads, int ld,
+                                                                              int ldkv, int ldo, float scale, int radius,
+                                                                              int anchor) {
+    constexpr int KK = D / 16, DB = D / 32, KSTR = D + 8, VSTR = D + 32;
+    constexpr int NS = 4, ROWS = 32 * NS;                          // tile slots, rows of the wave's region
+    extern __shared__ __attribute__((aligned(16))) char smem_ts[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long seq = (long long)blockIdx.x * WPB + wave;
+    if (seq >= nseq) return;                                       // (no workgroup barrier below: LDS regions are per wave)
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int head = (int)(seq % heads);
+    const long long bp = seq / heads;
+    const int p = (int)(bp % HW);
+    const int b = (int)(bp / HW);
+    const size_t base = ((size_t)b * T * HW + p);                  // q / k / v / out token row of frame 0
+    f16* wK = (f16*)smem_ts + (size_t)wave * (ROWS * (KSTR + VSTR));
+    f16* wV = wK + ROWS * KSTR;
+    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+
+    f16x8 qf[KK];
+    {
+        const f16* qp = q + (base + (size_t)(l31 < T ? l31 : 0) * HW) * ld + head * D + lh * 8;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) qf[kk] = l31 < T ? *(const f16x8*)(qp + kk * 16) : zero8;
+    }
+    // slot 0 <- tile 0, slot 2 <- tile 1, slots 1 and 3 <- zero (t_first = T: no row is read)
+    {
+        TemporalStreamTile<D> t0, t1, tz;
+        t0.load(k, v, base, HW, ldkv, head, T, 0, lane);
+        t1.load(k, v, base, HW, ldkv, head, T, 32, lane);
+        tz.load(k, v, base, HW, ldkv, head, T, T, lane);
+        t0.store(wK, wV, lane);
+        t1.store(wK + 64 * KSTR, wV + 64 * VSTR, lane);
+        tz.store(wK + 32 * KSTR, wV + 32 * VSTR, lane);
+        tz.store(wK + 96 * KSTR, wV + 96 * VSTR, lane);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this wave's LDS writes are in place
+    __builtin_amdgcn_wave_barrier();
+
+    const float c2 = scale * 1.4426950408889634f;
+    const int tr_off = (((lane & 15) >> 2) + 4 * lh) * VSTR + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    int sa = 3, sb = 1, sc = 2;                                    // the slots of tiles tq - 1, tq, tq + 1 (tile t: 1 + t % 3)
+#pragma unroll 1
+    for (int q0 = 0; q0 < T; q0 += 32) {
+        const int tq = q0 >> 5;
+        const int slot[NS] = {0, sa, sb, sc};
+        // tile tq + 2 travels to registers under this block's arithmetic (rows >= T, the last blocks: nothing is read)
+        TemporalStreamTile<D> nt;
+        nt.load(k, v, base, HW, ldkv, head, T, q0 + 64, lane);
+        // the next block's Q fragments are fetched under this block's arithmetic
+        f16x8 qn[KK];
+        {
+            const int qi = q0 + 32 + l31;
+            const f16* qp = q + (base + (size_t)(qi < T ? qi : 0) * HW) * ld + head * D + lh * 8;
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) qn[kk] = qi < T ? *(const f16x8*)(qp + kk * 16) : zero8;
+        }
+        // the rule as four words, as in the local kernel: tile 0 with anchor and band; band tiles with the band alone, which is
+        // empty by itself for a tile < 0 or >= ceil(T / 32) (lo >= 0, hi1 <= T) and is emptied for the band copy of tile 0
+        unsigned ml[NS];
+        {
+            const int qi = min(q0 + l31, T - 1);
+            const int lo = max(qi - radius, 0), hi1 = min(qi + radius, T - 1) + 1;
+            const auto below = [](int n) { return (unsigned)((1ull << min(max(n, 0), 32)) - 1ull); };
+            ml[0] = (below(anchor) | (below(hi1) & ~below(lo))) >> (4 * lh);
+#pragma unroll
+            for (int j = 1; j < NS; ++j) {
+                const int tt = tq + j - 2;
+                const unsigned band = below(hi1 - 32 * tt) & ~below(lo - 32 * tt);
+                ml[j] = (tt == 0 ? 0u : band) >> (4 * lh);
+            }
+        }
+        // ---- S^T tiles: s[j][r] = score(key = 32 tile(j) + (r & 3) + 8 (r >> 2) + 4 lh, query = q0 + l31) ----
+        f32x16 s[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[j][r] = 0.f;
+            const f16* kp = wK + (slot[j] * 32 + l31) * KSTR + lh * 8;
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) {
+                const f16x8 kf = *(const f16x8*)(kp + kk * 16);
+                s[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], s[j], 0, 0, 0);
+            }
+        }
+        float mx = -1e30f;
+#pragma unroll
+        for (int j = 0; j < NS; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                if (!(ml[j] & (1u << TL_SLOT(r)))) s[j][r] = -1e30f;
+                mx = fmaxf(mx, s[j][r]);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float mc = mx * c2;
+        float sum = 0.f;
+        f16x8 pf[NS][2];
+#pragma unroll
+        for (int j = 0; j < NS; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float pr = __builtin_amdgcn_exp2f(fmaf(s[j][r], c2, -mc));   // hidden keys: exp2(-huge) = 0
+                sum += pr;
+                pf[j][r >> 3][r & 7] = (f16)pr;
+            }
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = 1.0f / sum;
+
+        // ---- O^T[d][q] += V^T[d][key] P^T[key][q], k-slots as in the body file ----
+        f32x16 o[DB];
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+            const f16* vp = wV + tr_off + db * 32;
+#pragma unroll
+            for (int j = 0; j < NS; ++j)
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const f16x4 lo = lds_read_tr4(vp + (slot[j] * 32 + u * 16) * VSTR), hi = lds_read_tr4(vp + (slot[j] * 32 + u * 16 + 8) * VSTR);
+                    const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[j][u], o[db], 0, 0, 0);
+                }
+        }
+        // ---- ring refill: tile tq + 2 into the slot of tile tq - 1, after this block's last LDS read ----
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        nt.store(wK + sa * 32 * KSTR, wV + sa * 32 * VSTR, lane);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        if (q0 + l31 < T) {
+            f16* op = out + (base + (size_t)(q0 + l31) * HW) * ldo + head * D;
+#pragma unroll
+            for (int db = 0; db < DB; ++db)
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) {
+                    f16x4 w;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) w[e] = (f16)(o[db][4 * qd + e] * inv);
+                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;
+                }
+        }
+        const int s0 = sa;
+        sa = sb; sb = sc; sc = s0;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
+    }
+}
 #undef TL_SLOT
 
 // waves per workgroup: as many as keep a workgroup's LDS at or below 42 KB (D = 64) / 37 KB (D = 128), at least one
@@ -707,10 +917,10 @@ static int temporal_long_dispatch(int head_dim, int T, F&& f) {
     return MOFA_EINVAL;
 }
 
-// what the three entry points ask of their common arguments
+// what the three entry points ask of their common arguments (the streaming entry: the same with its own longest clip)
 static bool temporal_long_args_ok(const void* q, const void* k, const void* v, const void* out, int nclips, int T, int HW, int heads,
-                                  int head_dim, int ld, int ldkv, int ldo) {
-    if (!q || !k || !v || !out || nclips <= 0 || T < 1 || T > 128 || HW <= 0 || heads <= 0) return false;
+                                  int head_dim, int ld, int ldkv, int ldo, int max_T = 128) {
+    if (!q || !k || !v || !out || nclips <= 0 || T < 1 || T > max_T || HW <= 0 || heads <= 0) return false;
     if (head_dim != 64 && head_dim != 128) return false;
     return ld > 0 && ldkv > 0 && ldo > 0 && ld % 8 == 0 && ldkv % 8 == 0 && ldo % 8 == 0;
 }
@@ -764,6 +974,23 @@ extern "C" int mofa_attn_temporal_long_local_f16(const void* q, const void* k, c
             nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale,
             radius, anchor);
     });
+}
+
+// the local rule for 1 <= T <= 1024 frames under radius <= 32 and anchor <= 32 (attn_temporal_stream_local_kernel): the
+// KT = 4 geometry -- one wave per workgroup, four tile slots -- for every T
+extern "C" int mofa_attn_temporal_stream_local_f16(const void* q, const void* k, const void* v, void* out, int nclips, int T,
+                                                   int HW, int heads, int head_dim, int ld, int ldkv, int ldo, float scale,
+                                                   int radius, int anchor, mofa_stream_t stream) {
+    if (!temporal_long_args_ok(q, k, v, out, nclips, T, HW, heads, head_dim, ld, ldkv, ldo, 1024)) return MOFA_EINVAL;
+    if (radius < 0 || radius > 32 || anchor < 0 || anchor > 32 || anchor > T) return MOFA_EINVAL;
+    const long long nseq = (long long)nclips * HW * heads;
+    const auto launch = [&](auto g) {
+        using G = decltype(g);
+        return launch_temporal_long<G, attn_temporal_stream_local_kernel<G::D, G::WPB>>(
+            nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale,
+            radius, anchor);
+    };
+    return head_dim == 64 ? launch(TemporalLongGeom<64, 4>{}) : launch(TemporalLongGeom<128, 4>{});
 }
 
 // ---------------------------------------------------------------------------------------------------

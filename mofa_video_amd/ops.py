@@ -515,6 +515,27 @@ def attn_temporal_local(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, 
     return out
 
 
+def attn_temporal_local_stream(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=None, Tq=None, key_mask=None, local=None):
+    """``attn_temporal_local`` for clips of up to 1024 frames under a window of radius <= 32 and anchor <= min(T, 32), through
+    mofa_attn_temporal_stream_local_f16: the same rule, the same parameters in the same order, the same refusals; four key
+    tiles in LDS however long the clip is.  For T <= 128 it gives the bits of ``attn_temporal_local``."""
+    if key_mask is not None or Tq is not None:
+        raise ValueError("local temporal attention takes no key_mask and no Tq: the gathered-key path of frame-sharded clips has "
+                         "no per-query mask")
+    if local is None:
+        raise ValueError("local=(radius, anchor) is required; dense temporal attention is attn_temporal")
+    radius, anchor = (int(x) for x in local)
+    lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * T * HW, heads, head_dim, scale, out)
+    t0 = TIMER.start() if TIMER is not None else None
+    L.check(lib.mofa_attn_temporal_stream_local_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, T, HW, heads, head_dim,
+                                                    _ld(q), _ld(k), _ld(out), scale, radius, anchor, L.stream_ptr()),
+            "mofa_attn_temporal_stream_local_f16")
+    if t0 is not None:
+        Cc = heads * head_dim
+        TIMER.stop("attn_temporal_stream_kernel", t0, flops=4.0 * T * min(T, 128) * Cc * nclips * HW, nbytes=8.0 * nclips * T * HW * Cc)
+    return out
+
+
 def softmax_rows_(x):
     lib = L.load()
     L.check(lib.mofa_softmax_rows_f16(L.ptr(x), x.shape[0], x.shape[1], _ld(x), L.stream_ptr()), "mofa_softmax_rows_f16")

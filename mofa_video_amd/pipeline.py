@@ -62,6 +62,11 @@ class FlowControlNetPipelineOutput:
 
 MAX_TEMPORAL_FRAMES = 32        # mofa_attn_temporal_f16 holds one clip's keys in one score tile: the default limit per forward pass
 MAX_TEMPORAL_FRAMES_LONG = 128  # mofa_attn_temporal_long_f16 (four key tiles): what max_temporal_frames=... can raise it to
+# ... and what it can be raised to under a temporal_window of radius <= STREAM_RADIUS and anchor <= STREAM_ANCHOR, which
+# mofa_attn_temporal_stream_local_f16 runs with four key tiles in a ring.  That kernel takes 1024 frames; 256 is what the other
+# launches of a denoise step were read for (the row and offset arithmetic at 2 x 256 x 9216 rows)
+MAX_TEMPORAL_FRAMES_STREAM = 256
+STREAM_RADIUS = STREAM_ANCHOR = 32
 
 
 def _temporal_window(value):
@@ -169,7 +174,9 @@ class FlowControlNetPipeline:
         of every clip (mofa_video_amd/parallel.py); all ranks must call the pipeline with identical inputs.
         round_latents_to_fp16: round the latents to fp16 after every Euler step, as the reference's fp16 run does.
         max_temporal_frames: the most frames one forward pass may hold (``num_frames``, or ``window_size`` of the window
-        loop), 1 .. 128.  Above the default of 32 the temporal attention runs through mofa_attn_temporal_long_f16; clips
+        loop), 1 .. 128, or up to 256 under a ``temporal_window`` of radius <= 32 and anchor <= 32 (the temporal attention of
+        more than 128 frames is mofa_attn_temporal_stream_local_f16; nothing at full geometry has been run above 128 frames).
+        Above the default of 32 the temporal attention runs through mofa_attn_temporal_long_f16; clips
         sharded over ranks (``parallel``) stay limited to 32 unless the parallel object was built with ``max_key_slots=`` (up
         to 128): then to the smaller of the two.
         temporal_window: None (dense temporal attention, the default: today's launches), an integer radius, or (radius,
@@ -178,11 +185,15 @@ class FlowControlNetPipeline:
         being the conditioning frame.  In the Keypoint window loop the rule applies inside every window (a window is one
         forward pass of window_size frames).  Not available with a ``parallel`` object that shards frames.  Nothing is claimed
         about what the released checkpoints produce under it."""
-        if isinstance(max_temporal_frames, bool) or not isinstance(max_temporal_frames, int) \
-                or not 1 <= max_temporal_frames <= MAX_TEMPORAL_FRAMES_LONG:
-            raise ValueError(f"max_temporal_frames must be an integer in 1 .. {MAX_TEMPORAL_FRAMES_LONG}, got {max_temporal_frames!r}")
-        self.max_temporal_frames = max_temporal_frames
         self.temporal_window = _temporal_window(temporal_window)
+        streams = self.temporal_window is not None and self.temporal_window[0] <= STREAM_RADIUS \
+            and self.temporal_window[1] <= STREAM_ANCHOR
+        if isinstance(max_temporal_frames, bool) or not isinstance(max_temporal_frames, int) \
+                or not 1 <= max_temporal_frames <= (MAX_TEMPORAL_FRAMES_STREAM if streams else MAX_TEMPORAL_FRAMES_LONG):
+            raise ValueError(f"max_temporal_frames must be an integer in 1 .. {MAX_TEMPORAL_FRAMES_LONG}, or up to "
+                             f"{MAX_TEMPORAL_FRAMES_STREAM} with temporal_window=(radius <= {STREAM_RADIUS}, anchor <= "
+                             f"{STREAM_ANCHOR}), got {max_temporal_frames!r} with temporal_window={temporal_window!r}")
+        self.max_temporal_frames = max_temporal_frames
         self.vae, self.image_encoder, self.unet, self.controlnet = vae, image_encoder, unet, controlnet
         self.scheduler, self.feature_extractor = scheduler, feature_extractor
         self.vae_scale_factor = 8

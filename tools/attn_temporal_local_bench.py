@@ -6,7 +6,12 @@ stage the same bytes (q, k, v read + out written), so GB/s is on the same footin
 (dense, then the three rules), ROUNDS rounds of REPS launches each, events; a row gives the median over the rounds, the ratio
 local / dense of the medians, and for the dense row the run-to-run spread (max - min) / median over its rounds -- a ratio inside
 that spread says nothing.
-usage: python tools/attn_temporal_local_bench.py"""
+A second part times the streaming entry (mofa_attn_temporal_stream_local_f16, ops.attn_temporal_local_stream) on the same four
+shapes, in one process and on one set of buffers (allocated for 256 frames; a shorter clip uses their first rows): the local kernel
+at T = 128 under (12, 1) and (32, 1), the streaming entry at T = 128 on the same rows, and the streaming entry at T = 160 and 256.
+A row gives microseconds per launch, microseconds per frame and GB/s against the same 8 T HW C bytes per clip; the T = 128 rows
+also the ratio stream / local with the local row's spread.
+usage: python tools/attn_temporal_local_bench.py [--stream-only]"""
 import os
 import sys
 
@@ -40,7 +45,7 @@ def median(ts):
 
 
 worst_spread, ratios = 0.0, []
-for (B, HW, heads, hd, tag) in GEOMS:
+for (B, HW, heads, hd, tag) in ([] if "--stream-only" in sys.argv else GEOMS):
     for T in (49, 97, 128):
         Cc = heads * hd
         qkv = torch.randn(B * T * HW, 3 * Cc, device="cuda").half()
@@ -67,9 +72,38 @@ for (B, HW, heads, hd, tag) in GEOMS:
             ratios.append((t / td, spread, f"{tag} T{T} ({r}, {a})"))
             print(f"{shape} local ({r:3d}, {a}): {t * 1e6:8.1f} us  {nbytes / t / 1e9:6.0f} GB/s  local / dense {t / td:5.3f}", flush=True)
         del qkv, q, k, v, out
+if not ratios:
+    ratios = [(1.0, 0.0, "skipped")]
 lo, hi = min(ratios), max(ratios)
 slower = [r for r in ratios if r[0] > 1.0 + r[1]]
 print(f"# local / dense: {lo[0]:.3f} ({lo[2]}) .. {hi[0]:.3f} ({hi[2]}); largest dense spread {100 * worst_spread:.1f} %")
 print(f"# slower than dense by more than the dense spread of its shape: {len(slower)} of {len(ratios)} rows" + (":" if slower else ""))
 for x, s, what in slower:
     print(f"#   {what}: {x:.3f} (dense spread {100 * s:.1f} %)")
+
+# ---- the streaming entry: T = 128 beside the local kernel, then T = 160 and 256 ----
+TMAX = 256
+for (B, HW, heads, hd, tag) in GEOMS:
+    Cc = heads * hd
+    qkv = torch.randn(B * TMAX * HW, 3 * Cc, dtype=torch.float16, device="cuda")
+    out = torch.empty((B * TMAX * HW, Cc), dtype=torch.float16, device="cuda")
+    for loc in ((12, 1), (32, 1)):
+        def op(fn, T):
+            n = B * T * HW
+            return lambda: fn(qkv[:n, :Cc], qkv[:n, Cc:2 * Cc], qkv[:n, 2 * Cc:], B, T, HW, heads, head_dim=hd, out=out[:n], local=loc)
+        rows = [("local ", 128, op(ops.attn_temporal_local, 128))] + [("stream", T, op(ops.attn_temporal_local_stream, T)) for T in (128, 160, 256)]
+        for _, _, run in rows:
+            run()
+        torch.cuda.synchronize()
+        ts = [[] for _ in rows]
+        for _ in range(ROUNDS):
+            for i, (_, _, run) in enumerate(rows):
+                ts[i].append(timed(run))
+        t_local = median(ts[0])
+        for (name, T, _), tl in zip(rows, ts):
+            t, nbytes = median(tl), 4 * B * T * HW * Cc * 2
+            note = f"  spread {100 * (max(tl) - min(tl)) / t:4.1f} %" if name == "local " else \
+                f"  stream / local {t / t_local:5.3f}" if T == 128 else ""
+            print(f"attn temporal {tag:10s} {B}x{T}x{HW} {heads}h d{hd} {name} ({loc[0]:2d}, {loc[1]}): {t * 1e6:8.1f} us  "
+                  f"{t * 1e6 / T:7.2f} us/frame  {nbytes / t / 1e9:6.0f} GB/s{note}", flush=True)
+    del qkv, out
