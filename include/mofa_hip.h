@@ -58,7 +58,25 @@ int mofa_version(void);
  * models/unet_spatio_temporal_condition_controlnet.py:169-232, models/controlnet_sdv.py:259-309)
  * and the adapter's own convs (models/svdxt_featureflow_forward_controlnet_s2d_fixcmp_norefine.py:66-155).
  * ---------------------------------------------------------------------------------------- */
-enum { MOFA_MODE_PLAIN = 0, MOFA_MODE_CONV3X3 = 1, MOFA_MODE_CONVT3 = 2 };   /* CONV3X3 = k x k conv, k = ksize (1, 3, 5 or 7) */
+enum { MOFA_MODE_PLAIN = 0, MOFA_MODE_CONV3X3 = 1, MOFA_MODE_CONVT3 = 2,       /* CONV3X3 = k x k conv, k = ksize (1, 3, 5 or 7) */
+       MOFA_MODE_CONV3X3_UP2F = 3 };
+/* MOFA_MODE_CONV3X3_UP2F: the 3x3 convolution over a nearest-2x up-sampled image (CONV3X3 with up = 2: diffusers Upsample2D) with
+ * the up-sampling FOLDED into the weights.  Two of the three taps of an output pixel along an axis always read the same source
+ * pixel, so output (2y + a, 2x + b) depends only on source pixels {y - 1 + a, y + a} x {x - 1 + b, x + b}: four 2x2
+ * convolutions, one per output parity (a, b), on the low-resolution input -- 4 taps instead of 9, 4/9 of the MACs.
+ *   Hin, Win   the low-resolution image; Hout = 2 Hin, Wout = 2 Win; M = nimg * Hout * Wout output rows in the ordinary
+ *              (img, oy, ox) order at out + row * ldo; stride = 1, up = 2, ksize 0 or 3, dil 0 or 1, MOFA_PAD_SAME
+ *   w          fp16 [4][N][4 * Cin]: phase p = 2 a + b major, then output channel, then tap t = 2 ty + tx, then Cin; tap (ty, tx)
+ *              of phase (a, b) reads source pixel (y - 1 + a + ty, x - 1 + b + tx), zero outside the image -- exactly the taps
+ *              the classic form pads.  Each folded weight is the fp32 sum of the 1, 2 or 4 coinciding fp16 taps, rounded once
+ *              (mofa_video_amd/weights.py: fold_up2).
+ *   limits     the plain epilogue only (bias; no activation, row vector, residual or stats), the two 8-wave tiles only (a forced
+ *              4-wave tile is MOFA_EINVAL), Hin, Win <= 1024, at most 2047 images, and the 8-wave tiles' alignment rules: every
+ *              other combination is MOFA_EINVAL.
+ * Inside the kernels a 256-row tile belongs to ONE phase (it multiplies all its rows by one weight tile): the Mq = nimg * Hin * Win
+ * rows of a phase are padded to whole tiles, tiles_m = 4 * ceil(Mq / 256), row tile t holds rows 256 (t / 4) .. + 255 of phase
+ * t % 4 (the four passes over one input region are neighbours in the tile walk), and the epilogue scatters row (img, y, x) of
+ * phase (a, b) to output row (img * Hout + 2 y + a) * Wout + 2 x + b: mofa_igemm_up2f_row. */
 /* MOFA_ACT_GEGLU_PAIR: W holds the GEGLU projection with value and gate rows INTERLEAVED IN BLOCKS OF 16 (rows 32 b .. 32 b + 15 =
  * value rows of outputs 16 b .. 16 b + 15, rows 32 b + 16 .. 32 b + 31 = their gate rows; bias alike): out[m][16 b + c] =
  * s_acc * val * gelu(s_acc * gate), N / 2 output columns (diffusers GEGLU, erf GELU).  mofa_video_amd/weights.py packs it. */
@@ -129,6 +147,10 @@ typedef struct mofa_igemm_plan_t {
 } mofa_igemm_plan_t;
 /* MOFA_EINVAL for a NULL a or out, or n_cu <= 0; else MOFA_OK with the launch's own verdict in out->rc */
 int mofa_igemm_plan(const mofa_igemm_args* a, int n_cu, mofa_igemm_plan_t* out);
+/* MOFA_MODE_CONV3X3_UP2F: the output row that row `tile_row` (0 <= tile_row < 256 * tiles_m) of the kernels' phase-padded row
+ * tiles is stored to, or -1 for a padding row; MOFA_EINVAL for a tile_row out of range, another mode or arguments mofa_igemm_f16
+ * refuses.  Host only. */
+int64_t mofa_igemm_up2f_row(const mofa_igemm_args* a, int64_t tile_row);
 
 /* ------------------------------------------------------------------------------------------
  * Attention.  q/k/v are column blocks of token-major matrices: element (token, head, d) at

@@ -20,7 +20,7 @@ import torch
 
 from . import lib as L
 from . import ops
-from .weights import (f32, interleave_geglu, pack_conv3d_t3, pack_conv3x3, pack_ff320, pack_lin320, pack_linear, pad_rows)
+from .weights import (f32, fold_up2, interleave_geglu, pack_conv3d_t3, pack_conv3x3, pack_ff320, pack_lin320, pack_linear, pad_rows)
 
 BIG = 1 << 30
 # local temporal attention (Ctx.local): clips of up to this many frames go to ops.attn_temporal_local, whose kernel stages the
@@ -119,8 +119,30 @@ class Conv3x3:
         self.w = s.dev(pack_conv3x3(w))
         self.b = s.dev(f32(b))
         self.stride, self.up, self.pad = stride, up, pad
+        # nearest-2x + 3x3 (Upsample2D): also the up-sampling folded into 2x2 phase weights (4/9 of the MACs); the classic weight
+        # stays for the launches the folded mode does not take (CPU stand-ins, forced 4-wave tiles, epilogues other than plain)
+        self.wf = s.dev(fold_up2(w)) if up == 2 and stride == 1 and pad == L.PAD_SAME else None
+        self._fold = {}                                           # (H, W, rows, tile, strides, alignment) -> folded launch?
+
+    def _folded(self, x, H, W, kw):
+        if self.wf is None or not ops.UP2_FOLD or not x.is_cuda:
+            return False
+        if not set(kw) <= {"out", "split_k", "act", "stats", "tile"}:
+            return False
+        if kw.get("act", L.ACT_NONE) != L.ACT_NONE or kw.get("stats") or kw.get("tile") is not None:
+            return False
+        out = kw.get("out")
+        key = (H, W, x.shape[0], ops.FORCE_TILE, x.stride(0), x.data_ptr() & 15,
+               None if out is None else (out.stride(0), out.data_ptr() & 15))
+        ok = self._fold.get(key)
+        if ok is None:                                            # decided once: no planning inside captured steps
+            ok = self._fold[key] = ops.igemm_up2f_ok(x, self.wf, self.b, H, W, out)
+        return ok
 
     def __call__(self, x, H, W, **kw):
+        if self._folded(x, H, W, kw):
+            kw = {k: v for k, v in kw.items() if k in ("out", "split_k")}
+            return ops.igemm(x, self.wf, self.b, geom=ops.conv3x3_up2f_geom(H, W), **kw)
         return ops.igemm(x, self.w, self.b, geom=ops.conv3x3_geom(H, W, self.stride, self.up, pad=self.pad), **kw)
 
 

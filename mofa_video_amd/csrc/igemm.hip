@@ -491,6 +491,12 @@ extern "C" int mofa_igemm_f16(const mofa_igemm_args* a, mofa_stream_t stream) {
 
 extern "C" int mofa_igemm_stats_ok(const mofa_igemm_args* a) { return igemm320_stats_ok(a) ? 1 : 0; }
 
+extern "C" int64_t mofa_igemm_up2f_row(const mofa_igemm_args* a, int64_t tile_row) {
+    if (igemm_check_args(a) != MOFA_OK || a->mode != MOFA_MODE_CONV3X3_UP2F) return MOFA_EINVAL;
+    if (tile_row < 0 || tile_row >= 256ll * igemm_tiles_m(a, 256)) return MOFA_EINVAL;
+    return igemm_up2f_out_row(*a, (int)tile_row);
+}
+
 extern "C" int mofa_igemm_plan(const mofa_igemm_args* a, int n_cu, mofa_igemm_plan_t* out) {
     if (!a || !out || n_cu <= 0) return MOFA_EINVAL;
     *out = igemm_plan(a, n_cu);

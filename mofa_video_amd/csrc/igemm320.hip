@@ -83,10 +83,13 @@ struct Cursor3 {                    // one K-half plane of the persistent K-tile
 // whole tiles in the same persistent stream (the cursors prefetch it during the last whole tile's epilogue).
 // STATS: the epilogue also emits the GroupNorm pair sums of the outputs (mofa_igemm_args.stats); kinds 0 / 1 / 4 / 5, no
 // activation, no per-row vector (igemm320_stats_ok)
-template <int EPI, bool SPLIT = false, bool STATS = false>
+// UP2F: MOFA_MODE_CONV3X3_UP2F (plain epilogue only): row tiles of one phase each (igemm_plan.h), per-tile weight base and tap
+// origin, output rows through the row map
+template <int EPI, bool SPLIT = false, bool STATS = false, bool UP2F = false>
 __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_args a, const int tilesN, const int ntiles,
                                                               const Aux aux) {
     constexpr bool R1 = (EPI & EPI_R1) != 0, R2 = (EPI & EPI_R2) != 0, RV = (EPI & EPI_RV) != 0, GEGLU = (EPI & EPI_GEGLU) != 0;
+    typedef typename SelectT<UP2F, CursorUp2f<::Cursor3>, ::Cursor3>::type Cursor3;   // (UP2F: + the tile's phase)
     extern __shared__ __attribute__((aligned(16))) char smem[];   // the ONLY shared object
     TileWalk walk;
     walk.init(ntiles);
@@ -98,7 +101,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
     const int wm = wave / WN3, wn = wave - wm * WN3;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    const int taps = igemm_taps(a);
+    const int taps = kernel_taps<UP2F>(a);
     const int kpt = a.Cin / 64, nk = taps * kpt;
     const size_t Ktot = (size_t)taps * a.Cin;
 
@@ -140,27 +143,49 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
         item_decode(c.phase, c.local, tile, kb, ke);
         const int tm = fdiv(tile, aux.tiles_n), tn = tile - tm * tilesN;
         const int l = lane_now(lane), r_l = l >> 2;
-        const int g0 = pack_geo(a, aux, tm * TBM3 + 16 * wave + r_l), g1 = pack_geo(a, aux, tm * TBM3 + 16 * (wave + 8) + r_l);
-        c.gx0 = live ? g0 : -1;
-        c.gx1 = live ? g1 : -1;
-        const unsigned wo = (unsigned)(tn * TBN3 + 16 * wave + r_l) * (unsigned)(Ktot * 2) + swz_bytes(l, p);
-        c.wo0 = live ? wo : W_DEAD;
+        if constexpr (UP2F) {                                      // the tile's phase: its weight rows start at ph * N
+            const int g0 = pack_geo_up2f(a, aux, tm * TBM3 + 16 * wave + r_l), g1 = pack_geo_up2f(a, aux, tm * TBM3 + 16 * (wave + 8) + r_l);
+            c.gx0 = live ? g0 : -1;
+            c.gx1 = live ? g1 : -1;
+            c.ph = tm & 3;
+            // (the W rows of a column tile that reaches past N are NOT clamped: for phases 0-2 they are the next phase's weight rows,
+            // not the zeros the descriptor returns past the matrix -- columns >= N are never stored, by the epilogue or the fix-up)
+            const unsigned wo = (unsigned)(c.ph * a.N + tn * TBN3 + 16 * wave + r_l) * (unsigned)(Ktot * 2) + swz_bytes(l, p);
+            c.wo0 = live ? wo : W_DEAD;
+        } else {
+            const int g0 = pack_geo(a, aux, tm * TBM3 + 16 * wave + r_l), g1 = pack_geo(a, aux, tm * TBM3 + 16 * (wave + 8) + r_l);
+            c.gx0 = live ? g0 : -1;
+            c.gx1 = live ? g1 : -1;
+            const unsigned wo = (unsigned)(tn * TBN3 + 16 * wave + r_l) * (unsigned)(Ktot * 2) + swz_bytes(l, p);
+            c.wo0 = live ? wo : W_DEAD;
+        }
         c.ikc = 0; c.ksw = 0; c.ky = 0; c.kx = 0;
         c.kend = ke;
         if constexpr (SPLIT) {                                     // a slice may start in the middle of a tap
             int tap = fdiv(kb, aux.kpt_d);
             c.ikc = kb - tap * kpt;
             c.ksw = kb;
-            if (a.mode == MOFA_MODE_CONV3X3) { c.ky = fdiv(tap, aux.ks_d); c.kx = tap - c.ky * tg.ks; } else c.ky = tap;
-            c.xo0 = tap_src(a, aux, tg, c.gx0, c.ky, c.kx, swz_bytes(l, p));
-            c.xo1 = tap_src(a, aux, tg, c.gx1, c.ky, c.kx, swz_bytes(l, p));
+            if constexpr (UP2F) {
+                c.ky = tap >> 1; c.kx = tap & 1;
+                c.xo0 = tap_src_up2f(a, aux, c.gx0, c.ky, c.kx, c.ph, swz_bytes(l, p));
+                c.xo1 = tap_src_up2f(a, aux, c.gx1, c.ky, c.kx, c.ph, swz_bytes(l, p));
+            } else {
+                if (a.mode == MOFA_MODE_CONV3X3) { c.ky = fdiv(tap, aux.ks_d); c.kx = tap - c.ky * tg.ks; } else c.ky = tap;
+                c.xo0 = tap_src(a, aux, tg, c.gx0, c.ky, c.kx, swz_bytes(l, p));
+                c.xo1 = tap_src(a, aux, tg, c.gx1, c.ky, c.kx, swz_bytes(l, p));
+            }
         }
     };
     auto issue = [&](Cursor3& c, const int p, const int slot) __attribute__((always_inline)) {
         if (c.ikc == 0) {
             const int l = lane_now(lane);
-            c.xo0 = tap_src(a, aux, tg, c.gx0, c.ky, c.kx, swz_bytes(l, p));
-            c.xo1 = tap_src(a, aux, tg, c.gx1, c.ky, c.kx, swz_bytes(l, p));
+            if constexpr (UP2F) {
+                c.xo0 = tap_src_up2f(a, aux, c.gx0, c.ky, c.kx, c.ph, swz_bytes(l, p));
+                c.xo1 = tap_src_up2f(a, aux, c.gx1, c.ky, c.kx, c.ph, swz_bytes(l, p));
+            } else {
+                c.xo0 = tap_src(a, aux, tg, c.gx0, c.ky, c.kx, swz_bytes(l, p));
+                c.xo1 = tap_src(a, aux, tg, c.gx1, c.ky, c.kx, swz_bytes(l, p));
+            }
         }
         char* pl = smem + slot + p * PLANE;
         const int wk = c.ksw * 128;
@@ -171,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
         if (grp == p) bglds16(rsw, c.wo0 + wd2, wk, pl + XPL + (16 + (wave & 3)) * 1024);
     };
     auto advance = [&](Cursor3& c, const int p) __attribute__((always_inline)) {
-        tap_advance(c, a, kpt, tg.ks);
+        if constexpr (UP2F) tap_advance_up2f(c, kpt); else tap_advance(c, a, kpt, tg.ks);
         if (c.ksw == c.kend) { next_pos(c.phase, c.local); cur_setup(c, p); }
     };
 
@@ -338,7 +363,12 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
                 for (int p = 0; p < 4; ++p) {
                     const H16Piece r = h16_row<8>(eb, srow, lane, p);
                     const int mr = mw + 32 * i + r.row, n = nw + 32 * j0 + 8 * r.blk;
-                    if (mr < a.M && n + 8 <= a.N) *(f16x8*)(out + (size_t)mr * a.ldo + n) = r.v;
+                    if constexpr (UP2F) {                          // tile row -> output row (-1: padding row)
+                        const int orow = up2f_out_row(a, aux, mr);
+                        if (orow >= 0 && n + 8 <= a.N) *(f16x8*)(out + (size_t)orow * a.ldo + n) = r.v;
+                    } else if (mr < a.M && n + 8 <= a.N) {
+                        *(f16x8*)(out + (size_t)mr * a.ldo + n) = r.v;
+                    }
                 }
             }
             {                                                      // the single tile: 32 columns per row
@@ -354,7 +384,12 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
                 for (int p = 0; p < 2; ++p) {
                     const H16Piece r = h16_row<4>(eb, srow, lane, p);
                     const int mr = mw + 32 * i + r.row, n = nw + 32 * JS + 8 * r.blk;
-                    if (mr < a.M && n + 8 <= a.N) *(f16x8*)(out + (size_t)mr * a.ldo + n) = r.v;
+                    if constexpr (UP2F) {
+                        const int orow = up2f_out_row(a, aux, mr);
+                        if (orow >= 0 && n + 8 <= a.N) *(f16x8*)(out + (size_t)orow * a.ldo + n) = r.v;
+                    } else if (mr < a.M && n + 8 <= a.N) {
+                        *(f16x8*)(out + (size_t)mr * a.ldo + n) = r.v;
+                    }
                 }
             }
         }
@@ -827,6 +862,9 @@ __global__ __launch_bounds__(512, 2) void igemm320_f16_kernel(const mofa_igemm_a
                     else epilogue_res16(IC<1>{}, IC<0>{}, acc, mw, nw, eb);
                 }
             }
+        } else if constexpr (UP2F) {                               // (plain kind, no activation: igemm_check_args)
+            if (wn == 0) epilogue_light(IC<MOFA_ACT_NONE>{}, IC<0>{}, acc, mw, nw, eb);
+            else epilogue_light(IC<MOFA_ACT_NONE>{}, IC<1>{}, acc, mw, nw, eb);
         } else if (RV && idx_u < 0) {
             epilogue_rows(IC<0>{}, acc, mw, nw, eb);
         } else if (wn == 0) {
@@ -849,6 +887,7 @@ typedef void (*igemm320_kern_t)(const mofa_igemm_args, const int, const int, con
 
 // split-K fix-up: out = act(s_acc * (sum over the K slices + bias + rowvec[idx(m)]) + s1 r1 + s2 r2) for the R remainder tiles,
 // one thread per 8 output columns of a row; the slices are added in slice order (deterministic)
+template <bool UP2F = false>
 __global__ __launch_bounds__(256) void igemm320_fixup_kernel(const mofa_igemm_args a, const float* __restrict__ ws, const int tile0,
                                                              const int nsplit, const int tilesN, const int R) {
     constexpr int PPR = TBN3 / 8, PPT = TBM3 * PPR;   // pieces per row / per tile
@@ -857,8 +896,14 @@ __global__ __launch_bounds__(256) void igemm320_fixup_kernel(const mofa_igemm_ar
         const int r = (int)(idx / PPT), rem = (int)(idx - (long long)r * PPT);
         const int rr = rem / PPR, pc = rem - rr * PPR;
         const int tile = tile0 + r, tm = tile / tilesN, tn = tile - tm * tilesN;
-        const int m = tm * TBM3 + rr, n = tn * TBN3 + pc * 8;
-        if (m >= a.M || n + 8 > a.N) continue;
+        int m = tm * TBM3 + rr;
+        const int n = tn * TBN3 + pc * 8;
+        if constexpr (UP2F) {                                      // tile row -> output row (plain kind: no residual / row vector below)
+            m = igemm_up2f_out_row(a, m);
+            if (m < 0 || n + 8 > a.N) continue;
+        } else if (m >= a.M || n + 8 > a.N) {
+            continue;
+        }
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = 0.f;
@@ -936,6 +981,8 @@ __global__ __launch_bounds__(192) void igemm320_tile_stats_kernel(const f16* __r
 static const igemm320_kern_t k_igemm320[9] = {igemm320_f16_kernel<0>, igemm320_f16_kernel<1>, igemm320_f16_kernel<2>,
                                                igemm320_f16_kernel<3>, igemm320_f16_kernel<4>, igemm320_f16_kernel<5>,
                                                igemm320_f16_kernel<6>, nullptr, igemm320_f16_kernel<8>};
+// the folded nearest-2x + 3x3 mode: plain kind, whole tiles / with a split-K item
+static const igemm320_kern_t k_igemm320_up2f[2] = {igemm320_f16_kernel<0, false, false, true>, igemm320_f16_kernel<0, true, false, true>};
 static const igemm320_kern_t k_igemm320_split[7] = {
     igemm320_f16_kernel<0, true>, igemm320_f16_kernel<1, true>, igemm320_f16_kernel<2, true>, igemm320_f16_kernel<3, true>,
     igemm320_f16_kernel<4, true>, igemm320_f16_kernel<5, true>, igemm320_f16_kernel<6, true>};
@@ -949,6 +996,7 @@ static const igemm320_kern_t k_igemm320_split_stats[7] = {igemm320_f16_kernel<0,
 
 int igemm320_init() {
     return mofa_lds_optin(k_igemm320, LDS_BYTES3) == MOFA_OK && mofa_lds_optin(k_igemm320_split, LDS_BYTES3) == MOFA_OK &&
+                   mofa_lds_optin(k_igemm320_up2f, LDS_BYTES3) == MOFA_OK &&
                    mofa_lds_optin(k_igemm320_stats, LDS_BYTES3) == MOFA_OK && mofa_lds_optin(k_igemm320_split_stats, LDS_BYTES3) == MOFA_OK
                ? MOFA_OK
                : MOFA_ELAUNCH;
@@ -960,9 +1008,10 @@ static_assert(TBM3 == 256 && TBN3 == 320 && LDS_BYTES3 == 159744, "igemm_plan.h'
 int igemm320_launch(const mofa_igemm_args* a, const IgemmPlan& plan, hipStream_t stream) {
     const int kind = plan.kind, S = plan.split, R = plan.rem_tiles, tilesN = plan.tiles_n;
     Aux aux = igemm_pipe_aux(a, igemm_taps(*a), tilesN);
-    igemm320_kern_t kern = a->stats ? k_igemm320_stats[kind] : k_igemm320[kind];
+    const bool up2f = a->mode == MOFA_MODE_CONV3X3_UP2F;      // (kind 0, no stats: igemm_check_args)
+    igemm320_kern_t kern = up2f ? k_igemm320_up2f[0] : a->stats ? k_igemm320_stats[kind] : k_igemm320[kind];
     if (S > 1) {
-        kern = a->stats ? k_igemm320_split_stats[kind] : k_igemm320_split[kind];
+        kern = up2f ? k_igemm320_up2f[1] : a->stats ? k_igemm320_split_stats[kind] : k_igemm320_split[kind];
         aux.nsplit = S, aux.nsplit_d = fastdiv_make(S);
         aux.tile0 = plan.full_tiles, aux.nitems = R * S, aux.ws = (float*)a->workspace;
     }
@@ -970,7 +1019,11 @@ int igemm320_launch(const mofa_igemm_args* a, const IgemmPlan& plan, hipStream_t
     MOFA_CHECK_LAUNCH();
     if (S == 1) return MOFA_OK;
     const long long pieces = (long long)R * TBM3 * (TBN3 / 8);
-    hipLaunchKernelGGL(igemm320_fixup_kernel, dim3((int)((pieces + 255) / 256)), dim3(256), 0, stream, *a,
+    if (up2f)
+        hipLaunchKernelGGL(igemm320_fixup_kernel<true>, dim3((int)((pieces + 255) / 256)), dim3(256), 0, stream, *a,
+                           (const float*)a->workspace, plan.full_tiles, S, tilesN, R);
+    else
+        hipLaunchKernelGGL(igemm320_fixup_kernel<false>, dim3((int)((pieces + 255) / 256)), dim3(256), 0, stream, *a,
                        (const float*)a->workspace, plan.full_tiles, S, tilesN, R);
     MOFA_CHECK_LAUNCH();
     if (a->stats) {

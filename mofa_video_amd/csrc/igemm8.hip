@@ -64,11 +64,14 @@ struct Cursor {                     // one half-tile pair (X half h, W half h) o
 //   1 no stagger between the wave groups   2 no s_setprio   4 DMA issue before the fragment reads   8 no vmcnt wait
 //   16 no DMA inside the loop   32 no fragment reads inside the loop   64 per-segment cycle trace into aux.trace
 // (8, 16, 32 give wrong results: timing probes only)
-template <int EPI, int VAR = 0>
+// UP2F: MOFA_MODE_CONV3X3_UP2F (plain epilogue only): row tiles of one phase each (igemm_plan.h), per-tile weight base and tap
+// origin, output rows through the row map
+template <int EPI, int VAR = 0, bool UP2F = false>
 __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_args a, const int tilesN, const int ntiles,
                                                             const Aux aux) {
     constexpr bool GEGLU = (EPI & EPI_GEGLU) != 0, R1 = (EPI & EPI_R1) != 0, R2 = (EPI & EPI_R2) != 0,
                    RV = (EPI & EPI_RV) != 0;
+    typedef typename SelectT<UP2F, CursorUp2f<::Cursor>, ::Cursor>::type Cursor;   // (UP2F: + the tile's phase)
     extern __shared__ __attribute__((aligned(16))) char smem[];   // the ONLY shared object
     TileWalk walk;
     walk.init(ntiles);
@@ -79,7 +82,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
     const int wm = wave / WN, wn = wave - wm * WN;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    const int taps = igemm_taps(a);
+    const int taps = kernel_taps<UP2F>(a);
     const int kpt = a.Cin / BKS, nk = taps * kpt;
     const size_t Ktot = (size_t)taps * a.Cin;
 
@@ -101,13 +104,20 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
         const int tile = walk.start + (live ? c.local : 0);
         const int tm = fdiv(tile, aux.tiles_n), tn = tile - tm * tilesN;
         const int l = lane_now(lane), hr_l = 16 * wave + (l >> 3);
-        const int g0 = pack_geo(a, aux, tm * TBM + x_row(h, 0, hr_l)), g1 = pack_geo(a, aux, tm * TBM + x_row(h, 1, hr_l));
+        int g0, g1;
+        if constexpr (UP2F) {
+            g0 = pack_geo_up2f(a, aux, tm * TBM + x_row(h, 0, hr_l)), g1 = pack_geo_up2f(a, aux, tm * TBM + x_row(h, 1, hr_l));
+            c.ph = tm & 3;
+        } else {
+            g0 = pack_geo(a, aux, tm * TBM + x_row(h, 0, hr_l)), g1 = pack_geo(a, aux, tm * TBM + x_row(h, 1, hr_l));
+        }
         c.gx0 = live ? g0 : -1;
         c.gx1 = live ? g1 : -1;
         if (with_w) {
             auto w_off = [&](int hq) __attribute__((always_inline)) {
                 int n = tn * TBN + w_row(hq >> 1, hq & 1, hr_l);
                 n = n < a.N ? n : a.N - 1;
+                if constexpr (UP2F) n += c.ph * a.N;               // the phase's weight rows
                 const unsigned o = (unsigned)n * (unsigned)(Ktot * 2) + swz_bytes(l, hq & 1);
                 return live ? o : XO_INVALID;
             };
@@ -118,8 +128,13 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
     auto issue_x = [&](Cursor& c, const int h, const int bo) __attribute__((always_inline)) {
         if (c.ikc == 0) {
             const int l = lane_now(lane);
-            c.xo0 = tap_src(a, aux, tg, c.gx0, c.ky, c.kx, swz_bytes(l, 0));
-            c.xo1 = tap_src(a, aux, tg, c.gx1, c.ky, c.kx, swz_bytes(l, 1));
+            if constexpr (UP2F) {
+                c.xo0 = tap_src_up2f(a, aux, c.gx0, c.ky, c.kx, c.ph, swz_bytes(l, 0));
+                c.xo1 = tap_src_up2f(a, aux, c.gx1, c.ky, c.kx, c.ph, swz_bytes(l, 1));
+            } else {
+                c.xo0 = tap_src(a, aux, tg, c.gx0, c.ky, c.kx, swz_bytes(l, 0));
+                c.xo1 = tap_src(a, aux, tg, c.gx1, c.ky, c.kx, swz_bytes(l, 1));
+            }
         }
         bglds16(rsx, c.xo0, c.ikc * (BKS * 2), smem + bo + x_row(h, 0, 16 * wave) * RB);
         bglds16(rsx, c.xo1, c.ikc * (BKS * 2), smem + bo + x_row(h, 1, 16 * wave) * RB);
@@ -131,7 +146,7 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
         bglds16(rsw, c.wo3, c.ksw * (BKS * 2), smem + bo + SXB + w_row(1, 1, 16 * wave) * RB);
     };
     auto advance = [&](Cursor& c, const int h, const bool with_w) __attribute__((always_inline)) {
-        tap_advance(c, a, kpt, tg.ks);
+        if constexpr (UP2F) tap_advance_up2f(c, kpt); else tap_advance(c, a, kpt, tg.ks);
         if (c.ksw == nk) { c.local += walk.stride; cur_setup(c, h, with_w); }
     };
 
@@ -358,7 +373,12 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
                 for (int p = 0; p < 4; ++p) {
                     const H16Piece r = h16_row<4 * NJ>(scr, RowLines128{}, lane, p);
                     const int mr = mw + 32 * i + r.row, n = nw + 8 * r.blk;
-                    if (mr < a.M && n + 8 <= nout) *(f16x8*)(out + (size_t)mr * a.ldo + n) = r.v;
+                    if constexpr (UP2F) {                          // tile row -> output row (-1: padding row)
+                        const int orow = up2f_out_row(a, aux, mr);
+                        if (orow >= 0 && n + 8 <= nout) *(f16x8*)(out + (size_t)orow * a.ldo + n) = r.v;
+                    } else if (mr < a.M && n + 8 <= nout) {
+                        *(f16x8*)(out + (size_t)mr * a.ldo + n) = r.v;
+                    }
                 }
             }
         }
@@ -519,6 +539,8 @@ __global__ __launch_bounds__(512, 2) void igemm8_f16_kernel(const mofa_igemm_arg
         } else if constexpr (RV) {                                 // (row vector + activation launches run on the 4-wave tile)
             if (idx_u >= 0) epilogue_light(IC<MOFA_ACT_NONE>{}, IC<1>{}, acc, mw, nw, idx_u);
             else epilogue_light(IC<MOFA_ACT_NONE>{}, IC<0>{}, acc, mw, nw, 0);
+        } else if constexpr (UP2F) {                               // (no activation: igemm_check_args)
+            epilogue_light(IC<MOFA_ACT_NONE>{}, IC<0>{}, acc, mw, nw, 0);
         } else {
             if (a.act == MOFA_ACT_NONE) epilogue_light(IC<MOFA_ACT_NONE>{}, IC<0>{}, acc, mw, nw, 0);
             else if (a.act == MOFA_ACT_SILU) epilogue_light(IC<MOFA_ACT_SILU>{}, IC<0>{}, acc, mw, nw, 0);
@@ -542,7 +564,8 @@ typedef void (*igemm8_kern_t)(const mofa_igemm_args, const int, const int, const
 static const igemm8_kern_t k_igemm8[9] = {igemm8_f16_kernel<0>, igemm8_f16_kernel<1>, igemm8_f16_kernel<2>,
                                            igemm8_f16_kernel<3>, igemm8_f16_kernel<4>, igemm8_f16_kernel<5>,
                                            igemm8_f16_kernel<6>, igemm8_f16_kernel<7>, igemm8_f16_kernel<8>};
-
+// the folded nearest-2x + 3x3 mode: plain kind only
+static const igemm8_kern_t k_igemm8_up2f[1] = {igemm8_f16_kernel<0, 0, true>};
 
 #ifdef MOFA_PROBE
 // diagnostic hook of tools/igemm8_probe.py (tools/libmofa_hip_probe.so only; not part of the C ABI): plain-epilogue
@@ -564,7 +587,7 @@ extern "C" int mofa_igemm8_set_probe(int var, void* trace) {
 #endif
 
 int igemm8_init() {
-    if (mofa_lds_optin(k_igemm8, LDS_BYTES) != MOFA_OK) return MOFA_ELAUNCH;
+    if (mofa_lds_optin(k_igemm8, LDS_BYTES) != MOFA_OK || mofa_lds_optin(k_igemm8_up2f, LDS_BYTES) != MOFA_OK) return MOFA_ELAUNCH;
 #ifdef MOFA_PROBE
     if (mofa_lds_optin(k_probe_kern, LDS_BYTES) != MOFA_OK || mofa_lds_optin(k_trace_kern, LDS_BYTES) != MOFA_OK) return MOFA_ELAUNCH;
 #endif
@@ -575,7 +598,7 @@ int igemm8_launch(const mofa_igemm_args* a, const IgemmPlan& plan, hipStream_t s
     static_assert(TBM == 256 && TBN == 256 && LDS_BYTES == 163840, "igemm_plan.h's MOFA_TILE_256X256 row");
     const int kind = plan.kind;
     Aux aux = igemm_pipe_aux(a, igemm_taps(*a), plan.tiles_n);
-    igemm8_kern_t kern = k_igemm8[kind];
+    igemm8_kern_t kern = a->mode == MOFA_MODE_CONV3X3_UP2F ? k_igemm8_up2f[0] : k_igemm8[kind];
 #ifdef MOFA_PROBE
     aux.trace = s_probe_trace;
     if (kind == 0 && s_probe_var)

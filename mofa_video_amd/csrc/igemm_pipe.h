@@ -87,6 +87,45 @@ __device__ __forceinline__ unsigned tap_src(const mofa_igemm_args& a, const Aux&
     return ok ? off : XO_INVALID;
 }
 
+// ---- MOFA_MODE_CONV3X3_UP2F (the nearest-2x up-sampling folded into 2x2 phase weights; template flag UP2F of the kernels) -------
+// The instantiations of modes 0-2 call none of this and evaluate igemm_taps_classic, as before the mode existed.
+template <bool UP2F>
+__device__ __forceinline__ int kernel_taps(const mofa_igemm_args& a) {
+    if constexpr (UP2F) return 4; else return igemm_taps_classic(a);
+}
+template <bool B, class T, class F> struct SelectT { typedef T type; };
+template <class T, class F> struct SelectT<false, T, F> { typedef F type; };
+template <class C> struct CursorUp2f : C { int ph; };     // a kernel's cursor + the phase 2 a + b of the row tile it is in
+struct FDivBy { FastDiv d; __device__ __forceinline__ int operator()(int n) const { return fdiv(n, d); } };
+// tile row m (igemm_plan.h: row m & 255 of row tile m >> 8 = pixels 256 (m >> 10) .. of phase (m >> 8) & 3) -> img << 20 | y << 10 | x
+// of its SOURCE pixel (aux.hw / aux.wout divide by Hin * Win / Win in this mode), -1 for a padding row
+__device__ __forceinline__ int pack_geo_up2f(const mofa_igemm_args& a, const Aux& aux, int m) {
+    const IgemmUp2fPixel s = igemm_up2f_pixel(a, m, FDivBy{aux.hw}, FDivBy{aux.wout});   // (the one decode of igemm_plan.h)
+    const int g = (s.img << 20) | (s.y << 10) | s.x;
+    return s.valid ? g : -1;
+}
+// tap (ky, kx) of phase ph = 2 a + b reads source pixel (y - 1 + a + ky, x - 1 + b + kx): the CONV3X3 tap with ks = 2, stride = up = 1
+// and the per-axis origin 1 - a / 1 - b
+__device__ __forceinline__ unsigned tap_src_up2f(const mofa_igemm_args& a, const Aux& aux, int g, int ky, int kx, int ph, int swzb) {
+    const int vy = ((g >> 10) & 1023) + ky - (1 - (ph >> 1)), vx = (g & 1023) + kx - (1 - (ph & 1));
+    const bool ok = g >= 0 && vy >= 0 && vx >= 0 && vy < a.Hin && vx < a.Win;
+    const int row = ((g >> 20) * a.Hin + vy) * a.Win + vx;
+    const unsigned off = (unsigned)row * (unsigned)aux.ldxb + (unsigned)swzb;
+    return ok ? off : XO_INVALID;
+}
+template <class C>
+__device__ __forceinline__ void tap_advance_up2f(C& c, const int kpt) {
+    ++c.ksw;
+    if (++c.ikc == kpt) {
+        c.ikc = 0;
+        if (++c.kx == 2) { c.kx = 0; ++c.ky; }
+    }
+}
+// the output row of tile row mr, or -1 (the one row map of igemm_plan.h on the launch's magic-number dividers)
+__device__ __forceinline__ int up2f_out_row(const mofa_igemm_args& a, const Aux& aux, int mr) {
+    return igemm_up2f_out_row(a, mr, FDivBy{aux.hw}, FDivBy{aux.wout});
+}
+
 // a cursor (ikc, ksw: K tile within the tap / overall; ky, kx: tap coordinates, convT3: ky = tap) moves one K tile on
 template <class C>
 __device__ __forceinline__ void tap_advance(C& c, const mofa_igemm_args& a, const int kpt, const int ks) {
@@ -187,8 +226,9 @@ static inline FastDiv fastdiv_make(int d) {
 static inline Aux igemm_pipe_aux(const mofa_igemm_args* a, int taps, int tilesN) {
     Aux aux;
     aux.tiles_n = fastdiv_make(tilesN);
-    aux.hw = fastdiv_make(a->mode == MOFA_MODE_CONV3X3 ? a->Hout * a->Wout : 1);
-    aux.wout = fastdiv_make(a->mode == MOFA_MODE_CONV3X3 ? a->Wout : 1);
+    const bool up2f = a->mode == MOFA_MODE_CONV3X3_UP2F;      // (its rows are SOURCE pixels: divisors Hin * Win and Win)
+    aux.hw = fastdiv_make(up2f ? a->Hin * a->Win : a->mode == MOFA_MODE_CONV3X3 ? a->Hout * a->Wout : 1);
+    aux.wout = fastdiv_make(up2f ? a->Win : a->mode == MOFA_MODE_CONV3X3 ? a->Wout : 1);
     aux.t3hw = fastdiv_make(a->mode == MOFA_MODE_CONVT3 ? a->HW : 1);
     aux.t3t = fastdiv_make(a->mode == MOFA_MODE_CONVT3 && a->T > 0 ? a->T : 1);
     const bool halo = a->mode == MOFA_MODE_CONVT3 && a->T == 0;   // rows before a.x are read (tap -1 of the first frame)
@@ -196,7 +236,7 @@ static inline Aux igemm_pipe_aux(const mofa_igemm_args* a, int taps, int tilesN)
     aux.row_shift = halo ? a->HW : 0;
     aux.xbase = (const char*)a->x - (halo ? (size_t)a->HW * a->ldx * 2 : 0);
     aux.x_bytes = (unsigned)(igemm8_rows_in(a) * a->ldx * 2 - (a->ldx - a->Cin) * 2);
-    aux.w_bytes = (unsigned)((long long)a->N * taps * a->Cin * 2);
+    aux.w_bytes = (unsigned)(igemm_w_rows(a) * taps * a->Cin * 2);
     aux.trace = nullptr;
     aux.nsplit_d = fastdiv_make(1);
     aux.kpt_d = fastdiv_make(a->Cin / 64);

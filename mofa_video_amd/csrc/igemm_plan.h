@@ -23,8 +23,47 @@ static inline const IgemmTile& igemm_tile(int id) {
 static inline int igemm_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // (constexpr: host code here, and hipcc lets the kernels call a constexpr function too; always inlined there, as ever)
-__attribute__((always_inline)) constexpr int igemm_taps(const mofa_igemm_args& a) {
+// (igemm_taps_classic: modes 0-2 alone -- what the kernel instantiations of those modes evaluate, so that they compile to the
+// code they had before MOFA_MODE_CONV3X3_UP2F existed; the folded mode's instantiations know their 4 taps at compile time)
+__attribute__((always_inline)) constexpr int igemm_taps_classic(const mofa_igemm_args& a) {
     return (a.mode == MOFA_MODE_CONV3X3) ? (a.ksize > 0 ? a.ksize * a.ksize : 9) : (a.mode == MOFA_MODE_CONVT3 ? 3 : 1);
+}
+__attribute__((always_inline)) constexpr int igemm_taps(const mofa_igemm_args& a) {
+    return a.mode == MOFA_MODE_CONV3X3_UP2F ? 4 : igemm_taps_classic(a);
+}
+
+// ---- MOFA_MODE_CONV3X3_UP2F: the row tiles are NOT the output rows ------------------------------------------------------------
+// A 256-row tile multiplies all its rows by one weight tile, so it belongs to one phase p = 2 a + b: the Mq = M / 4 source pixels
+// (img, y, x) are padded to whole tiles per phase, and the phases are INTERLEAVED tile by tile: row tile t holds pixels
+// 256 (t >> 2) .. + 255 of phase t & 3.  The tile walk hands an XCD a contiguous range of tile ids (row tile major), so the four
+// passes over one 256-pixel input region (and its halo rows) run back to back on the same XCD and find the region in its L2;
+// phase-major order would put 1/4 of the launch between two reads of the same input rows.
+// Rows of the weight matrix [4 N][4 Cin] a launch addresses / its row tiles:
+static inline long long igemm_w_rows(const mofa_igemm_args* a) { return a->mode == MOFA_MODE_CONV3X3_UP2F ? 4ll * a->N : a->N; }
+static inline int igemm_tiles_m(const mofa_igemm_args* a, int tm) {
+    return a->mode == MOFA_MODE_CONV3X3_UP2F ? 4 * (int)((a->M / 4 + 255) / 256) : (int)(((long long)a->M + tm - 1) / tm);
+}
+// THE decode of a tile row r (row r & 255 of row tile r >> 8): its phase and source pixel; valid = 0 for a padding row.  The
+// producer side of the kernels (which source rows to fetch) and the row map below (where the result is stored) both start here.
+// div_hw / div_w divide by Hin * Win / Win (the kernels pass their magic-number dividers, the host plain division).
+struct IgemmUp2fPixel { int ph, img, y, x, valid; };
+template <class DivHW, class DivW>
+__attribute__((always_inline)) constexpr IgemmUp2fPixel igemm_up2f_pixel(const mofa_igemm_args& a, int r, DivHW div_hw, DivW div_w) {
+    const int q = ((r >> 10) << 8) | (r & 255);
+    const int img = div_hw(q), rem = q - img * (a.Hin * a.Win);
+    const int y = div_w(rem);
+    return IgemmUp2fPixel{(r >> 8) & 3, img, y, rem - y * a.Win, q < (a.M >> 2) ? 1 : 0};
+}
+// THE row map: tile row r -> the output row it is stored to, or -1 for a padding row
+template <class DivHW, class DivW>
+__attribute__((always_inline)) constexpr int igemm_up2f_out_row(const mofa_igemm_args& a, int r, DivHW div_hw, DivW div_w) {
+    const IgemmUp2fPixel s = igemm_up2f_pixel(a, r, div_hw, div_w);
+    const int o = (s.img * a.Hout + 2 * s.y + (s.ph >> 1)) * a.Wout + 2 * s.x + (s.ph & 1);
+    return s.valid ? o : -1;
+}
+struct IgemmPlainDiv { int d; constexpr int operator()(int n) const { return n / d; } };
+constexpr int igemm_up2f_out_row(const mofa_igemm_args& a, int r) {
+    return igemm_up2f_out_row(a, r, IgemmPlainDiv{a.Hin * a.Win}, IgemmPlainDiv{a.Win});
 }
 
 // the grid of the XCD-aware persistent tile walk (TileWalk, igemm_common.h): one workgroup per tile up to `slots` resident
@@ -36,7 +75,7 @@ static inline int igemm_grid(long long ntiles, int slots) {
 
 // rows of the activation buffer the launch may address (convT3 without clipping: one halo frame on either side)
 static inline long long igemm8_rows_in(const mofa_igemm_args* a) {
-    if (a->mode == MOFA_MODE_CONV3X3) return a->M / ((long long)a->Hout * a->Wout) * a->Hin * a->Win;
+    if (a->mode == MOFA_MODE_CONV3X3 || a->mode == MOFA_MODE_CONV3X3_UP2F) return a->M / ((long long)a->Hout * a->Wout) * a->Hin * a->Win;
     if (a->mode == MOFA_MODE_CONVT3 && a->T == 0) return (long long)a->M + 2ll * a->HW;
     return a->M;
 }
@@ -51,8 +90,10 @@ static inline bool igemm_pipe_eligible(const mofa_igemm_args* a, int kind, long 
     if (a->bias && (((uintptr_t)a->bias) & 15)) return false;
     if ((a->r1 || a->r2 || a->rowvec) && a->act != MOFA_ACT_NONE) return false;   // only the plain kind carries activation code here
     if (a->rowvec && (((uintptr_t)a->rowvec) & 15)) return false;
-    if ((long long)a->N * Ktot * 2 >= (1ll << 32) || (((uintptr_t)a->w) & 15)) return false;
-    if (a->mode == MOFA_MODE_CONV3X3) {
+    if (igemm_w_rows(a) * Ktot * 2 >= (1ll << 32) || (((uintptr_t)a->w) & 15)) return false;
+    if (a->mode == MOFA_MODE_CONV3X3_UP2F) {
+        if (a->M > 0x7fff0000) return false;                   // (padded tile rows stay below 2^31; Hin, Win, images: igemm_check_args)
+    } else if (a->mode == MOFA_MODE_CONV3X3) {
         const long long nimg = a->M / ((long long)a->Hout * a->Wout);
         if (a->Hout > 1024 || a->Wout > 1024 || nimg > 2047) return false;
     } else if (a->mode == MOFA_MODE_CONVT3) {
@@ -66,7 +107,7 @@ static inline bool igemm_pipe_eligible(const mofa_igemm_args* a, int kind, long 
 // accumulators and has no kernel there)
 static inline bool igemm320_eligible(const mofa_igemm_args* a, int kind, int taps) {
     if (kind == 7 || !igemm_pipe_eligible(a, kind, (long long)taps * a->Cin)) return false;
-    return (long long)(a->N + 320) * taps * a->Cin * 2 < 0x7ff00000LL;   // unclamped W row offsets stay below W_DEAD
+    return (igemm_w_rows(a) + 320) * taps * a->Cin * 2 < 0x7ff00000LL;   // unclamped W row offsets stay below W_DEAD
 }
 
 // can a launch with these arguments emit mofa_igemm_args.stats?  (a->stats itself is not looked at)
@@ -107,7 +148,7 @@ static inline int igemm_check_args(const mofa_igemm_args* a) {
     if (!a || !a->x || !a->w || !a->out) return MOFA_EINVAL;
     if (a->M <= 0 || a->N <= 0 || a->Cin <= 0) return MOFA_EINVAL;
     if (a->Cin % 64 != 0 || a->N % 4 != 0) return MOFA_EINVAL;
-    if (a->mode < 0 || a->mode > 2 || a->act < 0 || a->act > MOFA_ACT_GELU) return MOFA_EINVAL;
+    if (a->mode < 0 || a->mode > MOFA_MODE_CONV3X3_UP2F || a->act < 0 || a->act > MOFA_ACT_GELU) return MOFA_EINVAL;
     if (a->mode == MOFA_MODE_CONV3X3) {
         if (a->Hin <= 0 || a->Win <= 0 || a->Hout <= 0 || a->Wout <= 0) return MOFA_EINVAL;
         if ((a->stride != 1 && a->stride != 2) || (a->up != 1 && a->up != 2)) return MOFA_EINVAL;
@@ -115,6 +156,15 @@ static inline int igemm_check_args(const mofa_igemm_args* a) {
         if (a->dil < 0 || (a->dil > 1 && a->up != 1)) return MOFA_EINVAL;
         if (a->pad != MOFA_PAD_SAME && a->pad != MOFA_PAD_TRAILING) return MOFA_EINVAL;
         if (a->M % (a->Hout * a->Wout) != 0 || a->Hout > 65535 || a->Wout > 65535) return MOFA_EINVAL;
+    }
+    if (a->mode == MOFA_MODE_CONV3X3_UP2F) {                   // the folded nearest-2x + 3x3 (mofa_hip.h): plain epilogue, 8-wave tiles
+        if (a->Hin <= 0 || a->Win <= 0 || a->Hin > 1024 || a->Win > 1024) return MOFA_EINVAL;
+        if (a->Hout != 2 * a->Hin || a->Wout != 2 * a->Win || a->stride != 1 || a->up != 2) return MOFA_EINVAL;
+        if ((a->ksize != 0 && a->ksize != 3) || (a->dil != 0 && a->dil != 1) || a->pad != MOFA_PAD_SAME) return MOFA_EINVAL;
+        if (a->M % (a->Hout * a->Wout) != 0 || a->M / (a->Hout * a->Wout) > 2047) return MOFA_EINVAL;
+        if (a->act != MOFA_ACT_NONE || a->r1 || a->r2 || a->rowvec || a->stats) return MOFA_EINVAL;
+        if (a->tile == MOFA_TILE_128X128 || a->tile == MOFA_TILE_192X128) return MOFA_EINVAL;
+        if (!igemm_pipe_eligible(a, 0, 4ll * a->Cin)) return MOFA_EINVAL;   // no 4-wave kernel to fall back to: the 8-wave rules
     }
     if (a->mode == MOFA_MODE_CONVT3 && (a->T < 0 || a->HW <= 0 || (a->T > 0 && a->M % (a->T * a->HW) != 0)))
         return MOFA_EINVAL;
@@ -149,7 +199,7 @@ static inline int igemm_model_tile(const mofa_igemm_args* a, int kind, long long
     const double nk = (double)(Ktot / 64);
     int choice = 0;
     double best = 0;
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < 2 && a->mode != MOFA_MODE_CONV3X3_UP2F; ++k) {   // (the folded mode has no 4-wave kernel)
         const IgemmTile& c = igemm_tile(ids[k]);
         const long long t = (long long)igemm_cdiv(a->M, c.tm) * igemm_cdiv(a->N, c.tn);
         const long long slots_k = (long long)n_cu * c.wg_per_cu;
@@ -157,9 +207,9 @@ static inline int igemm_model_tile(const mofa_igemm_args* a, int kind, long long
         if (choice == 0 || cost < best) { best = cost; choice = ids[k]; }
     }
     {
-        const long long t = (long long)igemm_cdiv(a->M, 256) * igemm_cdiv(a->N, 256);
+        const long long t = (long long)igemm_tiles_m(a, 256) * igemm_cdiv(a->N, 256);
         const double cost = (double)((t + n_cu - 1) / n_cu) * 256 * 256 * 0.62 * (1.0 + epi8[kind] / nk);
-        if (cost < best) { best = cost; choice = MOFA_TILE_256X256; }
+        if (choice == 0 || cost < best) { best = cost; choice = MOFA_TILE_256X256; }
     }
     if (kind != 7) {
         // 256x320 (igemm320.hip): 0.58 per area (10 % less LDS-DMA, 7 % fewer fragment reads per flop than 256x256); its
@@ -169,7 +219,7 @@ static inline int igemm_model_tile(const mofa_igemm_args* a, int kind, long long
         // [1], [5] lowered from 10.0 / 10.5 in r03c so that the K = N = 320 residual launches leave the 192x128 tile (alone a
         // draw: 352-414 against 372-403 TF/s by box; in the clip - 0.27 %, profiles/archive/r03c_cost_model_and_splitk_ab.log:
         // beside a second stream the 17 % of padded columns of 3 x 128 are no longer free)
-        const long long t = (long long)igemm_cdiv(a->M, 256) * igemm_cdiv(a->N, 320);
+        const long long t = (long long)igemm_tiles_m(a, 256) * igemm_cdiv(a->N, 320);
         // a partial last round split along K (igemm320_split) costs 1 / S of a round + the fix-up pass.  QUIRK, kept as it
         // is: the model prices the split for ANY workspace pointer, while igemm_plan() below declines it for one that is not
         // 16-byte aligned -- such a launch is costed with a split it does not get.
@@ -210,8 +260,9 @@ static inline IgemmPlan igemm_plan_checked(const mofa_igemm_args* a, int n_cu) {
         if (forced) return refused;
         choice = chain[i + 1];
     }
+    if (a->mode == MOFA_MODE_CONV3X3_UP2F && choice != MOFA_TILE_256X320 && choice != MOFA_TILE_256X256) return refused;
     const IgemmTile& c = igemm_tile(choice);
-    const int tilesM = igemm_cdiv(a->M, c.tm), tilesN = igemm_cdiv(a->N, c.tn);
+    const int tilesM = igemm_tiles_m(a, c.tm), tilesN = igemm_cdiv(a->N, c.tn);
     const long long nt = (long long)tilesM * tilesN;
     if (nt > 0x7fffffffLL) return refused;
     if (a->stats && (((uintptr_t)a->stats) & 15)) return refused;

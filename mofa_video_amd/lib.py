@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (MOFA_HIP_LIB: another BUILD of the same library for same-box A/B runs of the test suite and the tools -- never a fallback)
 LIB_PATH = os.environ.get("MOFA_HIP_LIB") or os.path.join(_HERE, "libmofa_hip.so")
 
-MODE_PLAIN, MODE_CONV3X3, MODE_CONVT3 = 0, 1, 2
+MODE_PLAIN, MODE_CONV3X3, MODE_CONVT3, MODE_CONV3X3_UP2F = 0, 1, 2, 3
 ACT_NONE, ACT_SILU, ACT_GEGLU_PAIR, ACT_RELU, ACT_GELU = 0, 1, 2, 3, 4
 PAD_SAME, PAD_TRAILING = 0, 1
 SPARSE_ADD, SPARSE_LAST = 0, 1
@@ -93,6 +93,7 @@ PROTOTYPES = {
     "mofa_igemm_f16": [_P, _P],                     # (const mofa_igemm_args*: a byref(IgemmArgs) or the packed 192 bytes)
     "mofa_igemm_stats_ok": [_P],
     "mofa_igemm_plan": [_P, _I, _P],                # (const mofa_igemm_args*, n_cu, mofa_igemm_plan_t*: a byref(IgemmPlan)); no device call
+    "mofa_igemm_up2f_row": [_P, _L],                # (const mofa_igemm_args*, tile row) -> output row or -1; no device call
     "mofa_ff320_f16": [_P, _P],
     "mofa_lin320_f16": [_P, _P],                    # (const mofa_lin320_args*: the packed 112 bytes)                     # (const mofa_ff320_args*: the packed 152 bytes)
     "mofa_attn_spatial_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
@@ -159,7 +160,7 @@ PROTOTYPES = {
     "mofa_sparse_points_f32": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
     "mofa_flow_finish_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
 }
-_RESTYPE = {"mofa_softsplat_ws_bytes": C.c_int64, "mofa_flow_to_image_ws_bytes": C.c_int64}
+_RESTYPE = {"mofa_igemm_up2f_row": C.c_int64, "mofa_softsplat_ws_bytes": C.c_int64, "mofa_flow_to_image_ws_bytes": C.c_int64}
 
 _lib = None
 

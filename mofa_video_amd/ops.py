@@ -6,6 +6,7 @@ fine).  PyTorch only provides device memory and the stream here; all arithmetic 
 libmofa_hip.so.
 """
 import ctypes as C
+import os
 import struct
 import threading
 
@@ -101,6 +102,12 @@ def conv3x3_geom(H, W, stride=1, up=1, ksize=3, dil=1, pad=L.PAD_SAME):
     return ConvGeom(L.MODE_CONV3X3, H, W, Ho, Wo, stride, up, ksize=ksize, dil=dil, pad=pad)
 
 
+def conv3x3_up2f_geom(H, W):
+    """nearest-2x up-sampling + 3x3 convolution with the up-sampling folded into the weights (MODE_CONV3X3_UP2F: four 2x2
+    convolutions on the H x W input, one per output parity; weights.fold_up2 packs its [4N, 4 Cin] weight)"""
+    return ConvGeom(L.MODE_CONV3X3_UP2F, H, W, 2 * H, 2 * W, 1, 2, ksize=3, dil=1, pad=L.PAD_SAME)
+
+
 def convt3_geom(T, HW):
     return ConvGeom(L.MODE_CONVT3, T=T, HW=HW)
 
@@ -134,7 +141,28 @@ def igemm_workspace(device):
 # host time than everything else in this wrapper, and the host's time per launch is what bounds a frame-sharded rank
 _IGEMM_ARGS = struct.Struct("@7P22i3f3iPqP")
 assert _IGEMM_ARGS.size == C.sizeof(L.IgemmArgs)
-_TAPS_FIXED = {L.MODE_PLAIN: 1, L.MODE_CONVT3: 3}
+_TAPS_FIXED = {L.MODE_PLAIN: 1, L.MODE_CONVT3: 3, L.MODE_CONV3X3_UP2F: 4}
+
+# A/B switch (environment MOFA_UP2_FOLD=0|1, read once): blocks.Conv3x3 with up = 2 launches the folded form (4/9 of the MACs)
+UP2_FOLD = os.environ.get("MOFA_UP2_FOLD", "1") != "0"
+
+
+def igemm_up2f_ok(x, wf, bias, H, W, out=None):
+    """would ``mofa_igemm_f16`` take the folded launch of ``igemm(x, wf, bias, geom=conv3x3_up2f_geom(H, W), out=out)`` under the
+    current ``FORCE_TILE``?  Asked of the launcher's own plan (``mofa_igemm_plan``: host only, no device call)."""
+    lib = L.load()
+    nimg = x.shape[0] // (H * W)
+    if not x.is_cuda or nimg * H * W != x.shape[0]:
+        return False
+    N, Cin = wf.shape[0] // 4, wf.shape[1] // 4
+    args = _IGEMM_ARGS.pack(x.data_ptr(), wf.data_ptr(), bias.data_ptr() if bias is not None else 0, 0, 0, 0,
+                            out.data_ptr() if out is not None else 256,
+                            nimg * 4 * H * W, N, Cin, x.stride(0), out.stride(0) if out is not None else N, 0, 0, L.MODE_CONV3X3_UP2F,
+                            H, W, 2 * H, 2 * W, 1, 2, 3, 0, 0, 1, 1, 1, 1 << 30, L.ACT_NONE, 1.0, 1.0, 1.0, 1, L.PAD_SAME,
+                            FORCE_TILE, 256, IGEMM_WS_BYTES, 0)
+    plan = L.IgemmPlan()
+    n_cu = torch.cuda.get_device_properties(x.device).multi_processor_count
+    return lib.mofa_igemm_plan(args, n_cu, C.byref(plan)) == 0 and plan.rc == 0
 
 
 GN_STATS = True          # A/B switch: False = every GroupNorm takes its partial sums with mofa_gn_partial_f16 (three passes)
@@ -152,11 +180,14 @@ def igemm(x, w, bias=None, geom=PLAIN, M=None, rowvec=None, rv=(1, 1, 1, 1 << 30
     assert x.is_cuda and x.dtype is F16 and w.dtype is F16 and w.is_contiguous() and x.stride(1) == 1, "fp16 cuda, unit channel stride"
     N, Ktot = w.shape
     mode = geom.mode
+    if mode == L.MODE_CONV3X3_UP2F:                              # w is [4N, 4 Cin]: one [N, 4 Cin] matrix per output parity
+        assert N % 4 == 0
+        N //= 4
     taps = geom.ksize * geom.ksize if mode == L.MODE_CONV3X3 else _TAPS_FIXED[mode]
     Cin = Ktot // taps
     assert Cin * taps == Ktot and x.shape[1] >= Cin, (x.shape, w.shape, taps)
     if M is None:
-        if mode == L.MODE_CONV3X3:
+        if mode in (L.MODE_CONV3X3, L.MODE_CONV3X3_UP2F):
             nimg = x.shape[0] // (geom.Hin * geom.Win)
             assert nimg * geom.Hin * geom.Win == x.shape[0]
             M = nimg * geom.Hout * geom.Wout

@@ -30,6 +30,21 @@ def pack_conv3x3(w):
     return w.permute(0, 2, 3, 1).reshape(n, kh * kw * cin).to(torch.float16).contiguous()
 
 
+def fold_up2(w):
+    """nn.Conv2d weight [N, Cin, 3, 3] of a convolution that follows a nearest-2x up-sampling (diffusers Upsample2D) -> fp16
+    [4N, 4*Cinpad] for MOFA_MODE_CONV3X3_UP2F (include/mofa_hip.h): row (2a + b) * N + n, column (2 ty + tx) * Cinpad + c.
+    Output pixel (2y + a, 2x + b) reads the up-sampled rows 2y + a + ky - 1 = source rows (2y + a + ky - 1) >> 1: along an axis two
+    of the three taps always coincide, so phase a = 0 has the taps {ky 0} on source row y - 1 and {ky 1, ky 2} on y, phase a = 1
+    {ky 0, ky 1} on y and {ky 2} on y + 1.  The sums are formed in fp32 from the fp16-ROUNDED taps (what the classic launch
+    multiplies by) and rounded to fp16 once."""
+    w = _pad_cin(w, 1).to(torch.float16).to(torch.float32)
+    n, cin, kh, kw = w.shape
+    assert kh == 3 and kw == 3, w.shape
+    sel = torch.tensor([[[1., 0., 0.], [0., 1., 1.]], [[1., 1., 0.], [0., 0., 1.]]], device=w.device)   # [a][ty][ky]
+    f = torch.einsum("ayk,bxl,nckl->abnyxc", sel, sel, w)
+    return f.reshape(4 * n, 4 * cin).to(torch.float16).contiguous()
+
+
 def pack_conv3d_t3(w):
     """nn.Conv3d weight [N, Cin, 3, 1, 1] -> fp16 [N, 3*Cinpad], tap = kt major."""
     w = _pad_cin(w[..., 0, 0], 1)          # [N, Cin, 3]

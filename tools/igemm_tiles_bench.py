@@ -95,6 +95,47 @@ def make_call(mode, Mg, N, Cin, epi):
     return call, 2.0 * M * N * K
 
 
+# the six nearest-2x + 3x3 launches of a clip (UNet up blocks per denoise step, VAE up stages per 8-frame chunk): (n, Hin, Win), C
+UP2_SHAPES = [((50, 9, 16), 1280, "UNet up 28800x1280"), ((50, 18, 32), 1280, "UNet up 115200x1280"), ((50, 36, 64), 640, "UNet up 460800x640"),
+              ((8, 72, 128), 512, "VAE up 294912x512"), ((8, 144, 256), 512, "VAE up 1179648x512"), ((8, 288, 512), 256, "VAE up 4718592x256")]
+
+
+def up2_main(args):
+    """folded (MODE_CONV3X3_UP2F, weights.fold_up2) against classic (CONV3X3, up = 2) on the launcher's own tile: interleaved
+    rounds, ``--repeats`` repeats of the median of ``--rounds`` rounds each; ms per launch and the folded / classic ratio"""
+    from mofa_video_amd.weights import fold_up2, pack_conv3x3
+    print(f"{'shape':24s} {'rows':>8s} {'N':>5s} {'Cin':>5s}  classic ms (repeats)        folded ms (repeats)         ratio   spread")
+    for (n, H, W), Cc, tag in UP2_SHAPES:
+        x, w4 = h(n * H * W, Cc), h(Cc, Cc, 3, 3, scale=(9 * Cc) ** -0.5)
+        wc, wf, bias = pack_conv3x3(w4), fold_up2(w4), torch.randn(Cc, device=DEV)
+        out = torch.empty(4 * n * H * W, Cc, dtype=torch.float16, device=DEV)
+        calls = {"classic": lambda: ops.igemm(x, wc, bias, geom=ops.conv3x3_geom(H, W, up=2), out=out),
+                 "folded": lambda: ops.igemm(x, wf, bias, geom=ops.conv3x3_up2f_geom(H, W), out=out)}
+        for c in calls.values():
+            c()
+        torch.cuda.synchronize()
+        reps = {k: [] for k in calls}
+        for _ in range(args.repeats):
+            times = {k: [] for k in calls}
+            for _ in range(args.rounds):
+                for k, c in calls.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(args.iters):
+                        c()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    times[k].append(e0.elapsed_time(e1) / args.iters)
+            for k in calls:
+                reps[k].append(sorted(times[k])[len(times[k]) // 2])
+        mc, mf = sum(reps["classic"]) / args.repeats, sum(reps["folded"]) / args.repeats
+        spread = max(max(v) - min(v) for v in reps.values())
+        fmt = lambda v: " ".join(f"{t:7.3f}" for t in v)
+        print(f"{tag:24s} {4 * n * H * W:8d} {Cc:5d} {Cc:5d}  {fmt(reps['classic']):27s} {fmt(reps['folded']):27s} {mf / mc:5.3f}  {spread:6.3f}")
+        del x, wc, wf, out, calls
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=4)
@@ -104,11 +145,15 @@ def main():
     ap.add_argument("--only", default="", help="comma-separated substrings of the shape tags to run")
     ap.add_argument("--lib", default="", help="A/B: load this build of libmofa_hip.so instead of the in-tree one")
     ap.add_argument("--div", type=int, default=1, help="per-rank shapes of an N-GPU run: rows / N (N = 8: one CFG half x 4 frame shards)")
+    ap.add_argument("--up2", action="store_true", help="the six up-sampler launches, folded (MODE_CONV3X3_UP2F) against classic")
+    ap.add_argument("--repeats", type=int, default=3, help="--up2: repeats of the median over --rounds")
     args = ap.parse_args()
     if args.lib:
         lib.LIB_PATH = os.path.abspath(args.lib)
         print("library:", lib.LIB_PATH)
     lib.load()
+    if args.up2:
+        return up2_main(args)
     tiles = [t for t in TILES if t[0] in args.tiles.split(",")]
     shapes = SHAPES[:10] if args.quick else SHAPES
     if args.only:

@@ -31,7 +31,7 @@ def main():
     ops.TIMER = None
     bt = t.by_tag()
     tot = sum(v[1] for v in bt.values())
-    names = {0: "gemm", 1: "conv3x3", 2: "convT3", 9: "ff320", 10: "lin320"}
+    names = {0: "gemm", 1: "conv3x3", 2: "convT3", 3: "up2fold", 9: "ff320", 10: "lin320"}   # (3: MOFA_UP2_FOLD=0 runs them as conv3x3, u = 2)
     print(f"total igemm time {tot * 1e3:.1f} ms over {sum(v[0] for v in bt.values())} launches "
           f"({sum(v[2] for v in bt.values()) / tot / 1e12:.0f} TF/s)")
     print(f"{'kind':8s} {'s':>1s} {'u':>1s} {'M':>9s} {'N':>6s} {'K':>6s} {'act':>3s} {'n':>4s} {'ms':>8s} {'%':>5s} {'TF/s':>6s}")
