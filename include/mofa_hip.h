@@ -228,6 +228,24 @@ int mofa_attn_temporal_long_masked_f16(const void* q, const void* k, const void*
 int mofa_attn_temporal_long_local_f16(const void* q, const void* k, const void* v, void* out,
                                       int nclips, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
                                       float scale, int radius, int anchor, mofa_stream_t stream);
+/* Local temporal attention of a frame-sharded clip: the rule of mofa_attn_temporal_long_local_f16 on GLOBAL frame numbers,
+ * for Tq query frames (rows of q / out, clip stride Tq*HW; query row i is global frame q_frame0 + i) against 1 <= S <= 128
+ * key SLOTS (rows of k / v, clip stride S*HW) that hold only what those queries can see:
+ *     slots [0, anchor)   the global frames 0 .. anchor - 1
+ *     slot s >= anchor    the global frame band_frame0 + (s - anchor); the band has L = S - anchor slots
+ * Query row i (global frame g) sees slot s iff s < anchor, or s >= anchor and frame(s) >= anchor and |g - frame(s)| <= radius.
+ * A band slot that repeats an anchor frame (a shard next to the clip's start) is staged but has probability exactly 0, so
+ * every key counts once.  Precondition: K and V of all S slots are finite -- every slot is staged and an invisible one is
+ * multiplied by its zero probability (as for mofa_attn_temporal_long_local_f16).  Query rows >= Tq are neither read nor
+ * written.  Two equalities hold bit for bit: (a) with anchor = 0, q_frame0 = band_frame0 = 0 and Tq = S = T the output is that
+ * of mofa_attn_temporal_long_local_f16(radius, 0); (b) row i is row i of mofa_attn_temporal_long_masked_f16 called with the
+ * same Tq and T = S under the key mask {s : i sees s}.  MOFA_EINVAL for everything mofa_attn_temporal_long_f16 refuses (with S
+ * in place of T) and for Tq < 1, anchor < 0, anchor > S, radius < 0 (values above 127 are clamped: a band has at most 128
+ * slots), band_frame0 < 0 or above 2^30, q_frame0 < band_frame0 or q_frame0 + Tq > band_frame0 + L (every query's own frame
+ * lies in the band, so every query sees itself, directly or through its anchor slot) -- all checked before any device call. */
+int mofa_attn_temporal_long_window_f16(const void* q, const void* k, const void* v, void* out,
+                                       int nclips, int Tq, int S, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
+                                       float scale, int radius, int anchor, int q_frame0, int band_frame0, mofa_stream_t stream);
 /* Streaming local temporal self-attention over 1 <= T <= 1024 frames: the rule, the row layout and the scale convention of
  * mofa_attn_temporal_long_local_f16,
  *     query frame i sees key frame j  iff  j < anchor  or  |i - j| <= radius

@@ -69,7 +69,8 @@ def make_ctx(net, timestep, encoder_hidden_states, added_time_ids, B, T, base=No
     """The ``Ctx`` of one forward pass of ``net`` (anything with ``time``, ``temb_batch`` and ``device``: the UNet, an adapter).
     B, T = LOCAL batch / frame counts.  half: global CFG-half index when this rank computes one half only
     (encoder_hidden_states / added_time_ids are then still the global 2-row tensors); par: FrameParallel; local: (radius,
-    anchor) of local temporal attention -- every temporal layer of the pass attends under it -- or None for dense attention."""
+    anchor) of local temporal attention -- every temporal layer of the pass attends under it -- or None for dense attention.
+    Both together need a ``par`` built with ``window_keys=True`` (the band + anchor key exchange of parallel.FrameParallel)."""
     c = base if base is not None else Ctx(B, T)
     ts = torch.as_tensor(timestep, dtype=torch.float32, device=net.device).reshape(-1)
     ts = ts.expand(B).contiguous() if ts.numel() == 1 else ts.contiguous()
@@ -87,7 +88,7 @@ def make_ctx(net, timestep, encoder_hidden_states, added_time_ids, B, T, base=No
             c.half = half
         else:
             c.ctx16 = ops.cast_f32_to_f16(e)
-    if local is not None and par is not None:
+    if local is not None and par is not None and not getattr(par, "window_keys", False):
         raise ValueError("local temporal attention of frame-sharded clips: the gathered-key path has no per-query mask")
     c.par, c.local = par, local
     return c
@@ -486,7 +487,10 @@ class TransformerSpatioTemporal:
         fn = None
         if self.ff_in.can_fuse:
             f_own = None
-            if c.par is not None and c.par.kv_slots <= c.par.max_key_slots and c.par.kv_inplace and c.par.gather_hidden:
+            if c.par is not None and c.local is not None:
+                wplan = c.par.window_plan(*c.local)
+                hid, f_own = c.par.window_buffer(HW, self.C, h.device)        # norm1(f) straight into this shard's band slots
+            elif c.par is not None and c.par.kv_slots <= c.par.max_key_slots and c.par.kv_inplace and c.par.gather_hidden:
                 hid, f_own = c.par.kv_buffer(HW, self.C, h.device)            # norm1(f) straight into this shard's gather slot
             f, fn = self.ff_in.fused(h, pos=pos, HW=HW, T=T, ln_out=(self.tnorm1.g, self.tnorm1.b, f_own), ln_eps=self.tnorm1.eps)
         else:
@@ -498,6 +502,22 @@ class TransformerSpatioTemporal:
             else:
                 local = ops.attn_temporal_local if T <= LOCAL_STREAM_ABOVE else ops.attn_temporal_local_stream
                 a = local(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim, local=c.local)
+        elif c.local is not None:
+            # local temporal attention on a frame shard (par.window_keys): this rank's queries see their band and the anchor
+            # frames only, so the key buffer holds anchor + T + 2 radius frames at most instead of the clip.  LayerNorm writes
+            # the own frames into their band slots, the neighbours' radius frames and shard 0's anchor frames arrive while the
+            # Q projection runs, and ONE K|V projection covers the S slots.
+            Cc, par = self.C, c.par
+            if fn is None:
+                wplan = par.window_plan(*c.local)
+                hid, own = par.window_buffer(HW, Cc, f.device)
+                fn = self.tnorm1(f, out=own)
+            work = par.window_begin(hid, HW)
+            q = self.tattn1.q(fn)
+            work.wait()
+            kv = ops.igemm(hid, self.tattn1.wqkv[Cc:])
+            a = ops.attn_temporal_window(q, kv[:, :Cc], kv[:, Cc:], 1, wplan.S, HW, self.heads, head_dim=self.tattn1.head_dim,
+                                         Tq=T, local=c.local, q_frame0=par.f0, band_frame0=wplan.b0)
         else:
             # this rank holds T of the clip's T_full frames.  The K|V projection writes this shard's slot of the gather
             # buffer, one all_gather_into_tensor (asynchronous, RCCL's stream) fills the other slots while the Q

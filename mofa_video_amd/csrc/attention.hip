@@ -17,7 +17,8 @@
 //   key tiles of K and V in the wave's LDS, one 32-query block at a time with all of its score tiles in registers.
 //   mofa_attn_temporal_long_masked_f16: its form for frame-sharded clips (Tq <= T query frames, a key mask);
 //   mofa_attn_temporal_long_local_f16: its form under a per-query rule (a band round the query plus the first frames).
-//   One body (attn_temporal_long_body.inc) included by the three kernels, one launcher, one dispatch, one argument check.
+//   mofa_attn_temporal_long_window_f16: that rule for a frame shard (Tq query frames, key slots = anchor frames + band frames).
+//   One body (attn_temporal_long_body.inc) included by the four kernels, one launcher, one dispatch, one argument check.
 //
 // mofa_transpose_v_f16, mofa_softmax_rows_f16: the two helpers of the VAE mid-block attention (scores materialised by implicit GEMMs).
 
@@ -596,11 +597,12 @@ extern "C" int mofa_attn_temporal_f16(const void* q, const void* k, const void* 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Long temporal attention: 1 <= T <= 128 key frames per clip.  ONE body, attn_temporal_long_body.inc, included by three kernels
+// Long temporal attention: 1 <= T <= 128 key frames per clip.  ONE body, attn_temporal_long_body.inc, included by four kernels
 // that differ only in the five rule macros they define for it (the .inc names them and says what is shared):
 //   attn_temporal_long_kernel         self-attention, keys < T
 //   attn_temporal_long_masked_kernel  frame-sharded clips: Tq <= T query frames against T key SLOTS under a 128-bit mask
 //   attn_temporal_long_local_kernel   self-attention under a per-query rule: a band round the query + the first frames
+//   attn_temporal_long_window_kernel  frame-sharded clips under that rule: Tq query frames against anchor + band key SLOTS
 // The body is shared as TEXT, not as an always-inlined function taking a rule object: with the body in a __device__ function
 // behind one-line __global__ wrappers the compiler no longer keeps the Q-fragment arrays as one wide value -- the dense kernel's
 // own text moved into such a function, nothing else changed, shows it -- and the D = 128 instantiations ran 0.4-1.1 % slower
@@ -664,6 +666,39 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_long_local_kernel(cons
 #define TL_WORDS(q0)                                                                                                \
     const int qi = min((q0) + l31, T - 1);                                                                          \
     const int lo = max(qi - radius, 0), hi1 = min(qi + radius, T - 1) + 1;                                          \
+    unsigned ml[KT];                                                                                                \
+    _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) {                                                             \
+        const auto below = [](int n) { return (unsigned)((1ull << min(max(n, 0), 32)) - 1ull); };                   \
+        ml[kt] = (below(anchor - 32 * kt) | (below(hi1 - 32 * kt) & ~below(lo - 32 * kt))) >> (4 * lh);             \
+    }
+#define TL_HIDDEN(kt, r) (!(ml[kt] & (1u << TL_SLOT(r))))
+#include "attn_temporal_long_body.inc"
+}
+
+// Window: the local rule on the key buffer of a frame shard -- Tq query rows (global frames q_frame0 .. q_frame0 + Tq - 1)
+// against T key SLOTS: slots [0, anchor) hold the global frames 0 .. anchor - 1, slot s >= anchor holds the global frame
+// band_frame0 + (s - anchor).  Rectangular like the masked kernel, per-query words like the local kernel.  A query of global
+// frame g sees every anchor slot, and band slot s iff its frame f >= anchor (a band slot that repeats an anchor frame is staged
+// but hidden: every key counts once) and |g - f| <= radius.  In slot space that is [lo, hi1) with
+//   lo  = anchor + max(g - radius, anchor, band_frame0) - band_frame0    (>= anchor)
+//   hi1 = anchor + min(g + radius, band_frame0 + L - 1) - band_frame0 + 1    (<= T; L = T - anchor band slots)
+// and lo >= hi1 (a query below the anchor whose band lies inside the anchor frames) leaves the band empty.  The host passes
+// radius <= 127, 0 <= anchor <= T and band_frame0 <= q_frame0, q_frame0 + Tq <= band_frame0 + L, so every query's own frame
+// is in the band or among the anchors and no row is empty.  All T slots are staged: K and V of every slot must be finite.
+// Query rows >= Tq are not stored and take the words of row Tq - 1.
+template <int D, int KT, int WPB>
+__global__ __launch_bounds__(64 * WPB) void attn_temporal_long_window_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                             const f16* __restrict__ v, f16* __restrict__ out,
+                                                                             long long nseq, int Tq, int T, int HW, int heads,
+                                                                             int ld, int ldkv, int ldo, float scale, int radius,
+                                                                             int anchor, int q_frame0, int band_frame0) {
+#define TL_TQ Tq
+#define TL_STAGE_WORD(t0)
+#define TL_STAGED(t) ((t) < T)
+#define TL_WORDS(q0)                                                                                                \
+    const int g = q_frame0 + min((q0) + l31, Tq - 1);                                                               \
+    const int lo = anchor + max(max(g - radius, anchor), band_frame0) - band_frame0;                                \
+    const int hi1 = anchor + min(g + radius, band_frame0 + (T - anchor) - 1) - band_frame0 + 1;                     \
     unsigned ml[KT];                                                                                                \
     _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) {                                                             \
         const auto below = [](int n) { return (unsigned)((1ull << min(max(n, 0), 32)) - 1ull); };                   \
@@ -973,6 +1008,25 @@ extern "C" int mofa_attn_temporal_long_local_f16(const void* q, const void* k, c
         return launch_temporal_long<G, attn_temporal_long_local_kernel<G::D, G::KT, G::WPB>>(
             nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale,
             radius, anchor);
+    });
+}
+
+// the local rule on a frame shard's key buffer: Tq query frames from global frame q_frame0 on against S slots = `anchor` anchor
+// frames + the band frames band_frame0 .. band_frame0 + (S - anchor) - 1 (attn_temporal_long_window_kernel).  The queries' own
+// frames must lie in the band (the last two rules); band_frame0 above 2^30 is refused so that no frame sum overflows an int
+extern "C" int mofa_attn_temporal_long_window_f16(const void* q, const void* k, const void* v, void* out, int nclips, int Tq,
+                                                  int S, int HW, int heads, int head_dim, int ld, int ldkv, int ldo, float scale,
+                                                  int radius, int anchor, int q_frame0, int band_frame0, mofa_stream_t stream) {
+    if (!temporal_long_args_ok(q, k, v, out, nclips, S, HW, heads, head_dim, ld, ldkv, ldo) || Tq < 1) return MOFA_EINVAL;
+    if (radius < 0 || anchor < 0 || anchor > S || band_frame0 < 0 || band_frame0 > (1 << 30)) return MOFA_EINVAL;
+    if (q_frame0 < band_frame0 || (long long)q_frame0 + Tq > (long long)band_frame0 + (S - anchor)) return MOFA_EINVAL;
+    if (radius > 127) radius = 127;
+    const long long nseq = (long long)nclips * HW * heads;
+    return temporal_long_dispatch(head_dim, S, [&](auto g) {
+        using G = decltype(g);
+        return launch_temporal_long<G, attn_temporal_long_window_kernel<G::D, G::KT, G::WPB>>(
+            nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, Tq, S, HW, heads, ld, ldkv, ldo, scale,
+            radius, anchor, q_frame0, band_frame0);
     });
 }
 

@@ -546,6 +546,41 @@ def attn_temporal_local(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, 
     return out
 
 
+def window_visible_keys(S, Tq, radius, anchor, q_frame0, band_frame0):
+    """how many (query, key slot) pairs of ``attn_temporal_window`` are visible: per query its anchor slots plus the band frames
+    >= anchor within ``radius`` of it (a band slot that repeats an anchor frame is not counted: its probability is 0)"""
+    hi_f = band_frame0 + (S - anchor) - 1
+    n = 0
+    for g in range(q_frame0, q_frame0 + Tq):
+        n += anchor + max(0, min(g + radius, hi_f) - max(g - radius, anchor, band_frame0) + 1)
+    return n
+
+
+def attn_temporal_window(q, k, v, nclips, S, HW, heads, head_dim=64, scale=None, out=None, Tq=None, local=None, q_frame0=0,
+                         band_frame0=0):
+    """``attn_temporal_local`` for a frame shard, through mofa_attn_temporal_long_window_f16: q holds Tq frames per clip (global
+    frames q_frame0 .. q_frame0 + Tq - 1; Tq=None: S), k / v hold S <= 128 key slots per clip -- the first ``anchor`` slots are the
+    global frames 0 .. anchor - 1, the others the band frames band_frame0 .. band_frame0 + (S - anchor) - 1 -- and local =
+    (radius, anchor) is the rule on GLOBAL frames: a query sees the anchor slots and the band frames >= anchor within ``radius``
+    of it (a band slot that repeats an anchor frame has probability 0).  The queries' frames must lie in the band; K and V of
+    every slot must be finite."""
+    if local is None:
+        raise ValueError("local=(radius, anchor) is required; the dense sharded attention is attn_temporal_sharded")
+    radius, anchor = (int(x) for x in local)
+    Tq = S if Tq is None else Tq
+    lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * Tq * HW, heads, head_dim, scale, out)
+    t0 = TIMER.start() if TIMER is not None else None
+    L.check(lib.mofa_attn_temporal_long_window_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, Tq, S, HW, heads, head_dim,
+                                                   _ld(q), _ld(k), _ld(out), scale, radius, anchor, int(q_frame0), int(band_frame0),
+                                                   L.stream_ptr()), "mofa_attn_temporal_long_window_f16")
+    if t0 is not None:
+        Cc = heads * head_dim
+        TIMER.stop("attn_temporal_long_kernel", t0,
+                   flops=4.0 * window_visible_keys(S, Tq, radius, anchor, int(q_frame0), int(band_frame0)) * Cc * nclips * HW,
+                   nbytes=4.0 * nclips * (Tq + S) * HW * Cc)
+    return out
+
+
 def attn_temporal_local_stream(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=None, Tq=None, key_mask=None, local=None):
     """``attn_temporal_local`` for clips of up to 1024 frames under a window of radius <= 32 and anchor <= min(T, 32), through
     mofa_attn_temporal_stream_local_f16: the same rule, the same parameters in the same order, the same refusals; four key

@@ -16,6 +16,9 @@ Weights are replicated.  Exchanges inside one denoise step (RCCL over xGMI throu
       a preallocated [frame_ranks x T_max frames] buffer (the LayerNorm writes this rank's slot in place, the collective runs
       asynchronously under the Q projection, every rank then projects K|V for all key slots, and the attention kernel masks
       the padding frames of uneven shards -- no pad / concat / compaction copies)                   (frame group)
+      Under a temporal window on a FrameParallel built with ``window_keys=True`` instead: ``radius`` frames to and from each
+      neighbour shard (batched p2p, "data") and the anchor frames from shard 0 (one broadcast, bulk) into a [anchor + band
+      frames] buffer, K|V projected for those slots only, mofa_attn_temporal_long_window_f16 -- never run on more than one GPU
     * CFG combine: the two halves of one frame shard swap their noise predictions                 (pair group)
 and once per clip: all-gather of the final latents before the VAE decode, whose chunks are independent and are
 dealt round-robin to ALL ranks.  Everything per-frame (2-D convs, spatial norms/attention, FFs, the adapter warps,
@@ -179,6 +182,29 @@ class TorchComm:
             ops += [dist.P2POp(dist.isend, last.contiguous(), next_rank, group=grp), dist.P2POp(dist.irecv, from_next, next_rank, group=grp)]
         return _HaloWork(dist.batch_isend_irecv(ops) if ops else [], from_prev, from_next, (first, last))
 
+    def window_begin(self, to_prev, to_next, from_prev, from_next, prev_rank, next_rank, anchors, ranks, lane=0):
+        """The exchange of windowed temporal attention (FrameParallel.window_begin), received IN PLACE: ``to_prev`` / ``to_next``
+        (views of this rank's frames) go to the neighbour shards and their blocks arrive in ``from_prev`` / ``from_next`` (views
+        of the key buffer) by batched p2p on the lane's "data" communicator; ``anchors`` (a view of the key buffer, or None) is
+        broadcast from shard 0 -- ranks[0], whose view already holds the frames -- on the lane's bulk communicator.  A side that
+        has no neighbour or no frames to move passes None for its views.  Every rank issues the same sequence: the p2p batch,
+        then the broadcast.  ``wait()`` makes the current stream wait."""
+        dist = self.dist
+        grp = self._lane(lane)["data"][tuple(ranks)]
+        ops, keep = [], []
+        for send, recv, peer in ((to_prev, from_prev, prev_rank), (to_next, from_next, next_rank)):
+            if peer is None:
+                continue
+            if send is not None:
+                keep.append(send.contiguous())
+                ops.append(dist.P2POp(dist.isend, keep[-1], peer, group=grp))
+            if recv is not None:
+                ops.append(dist.P2POp(dist.irecv, recv, peer, group=grp))
+        works = list(dist.batch_isend_irecv(ops)) if ops else []
+        if anchors is not None and len(ranks) > 1:
+            works.append(dist.broadcast(anchors, src=ranks[0], group=self._lane(lane)["bulk"][tuple(ranks)], async_op=True))
+        return _HaloWork(works, None, None, keep)
+
 
 class _Done:
     def wait(self):
@@ -283,19 +309,44 @@ class ThreadComm:
         from_next = got[ranks.index(next_rank)][0] if next_rank is not None else None
         return _HaloWork([], from_prev, from_next)
 
+    def window_begin(self, to_prev, to_next, from_prev, from_next, prev_rank, next_rank, anchors, ranks, lane=0):
+        """TorchComm.window_begin on virtual ranks: the neighbours' blocks and shard 0's anchor frames copied into the views"""
+        if len(ranks) == 1:
+            return _Done()
+        ranks = list(ranks)
+        first = ranks.index(self.rank) == 0
+        got = self._exchange((to_prev, to_next, anchors if first else None), ranks)
+        if from_prev is not None:
+            from_prev.copy_(got[ranks.index(prev_rank)][1])
+        if from_next is not None:
+            from_next.copy_(got[ranks.index(next_rank)][0])
+        if anchors is not None and not first:
+            anchors.copy_(got[0][2])
+        return _Done()
+
 
 # ---------------------------------------------------------------------------------------------------------
 class FrameParallel:
     """The per-rank object blocks consult (``Ctx.par``) when a clip's frames are sharded."""
 
-    def __init__(self, layout, comm, p2p=True, max_key_slots=32):
+    def __init__(self, layout, comm, p2p=True, max_key_slots=32, window_keys=False):
         """max_key_slots: the most key slots (frame_ranks x largest shard) the temporal attention takes from the gathered
         buffer in place, 32 .. 128.  The default of 32 is the T <= 32 masked kernel; above it clips of up to that many frames
         may be sharded and their attention runs through mofa_attn_temporal_long_masked_f16 (``ops.attn_temporal_sharded``).
-        A layout whose padded slots exceed the limit compacts to T_full frames first."""
+        A layout whose padded slots exceed the limit compacts to T_full frames first.
+        window_keys: opt in to local temporal attention (a pipeline's ``temporal_window``, ``Ctx.local``) on this frame shard.  A
+        query then needs its band and the anchor frames only, so the temporal layers exchange ``radius`` frames with each
+        neighbour shard and take the anchor frames from shard 0 (``window_plan`` / ``window_buffer`` / ``window_begin``) instead
+        of gathering the clip, and attend through mofa_attn_temporal_long_window_f16.  The key slots of a rank, anchor + T_max + 2
+        radius <= 128, bound what can be sharded, not the clip length and not ``max_key_slots``.  Dense attention on such an
+        object is unchanged.  Nothing of this path has run on more than one GPU: it is checked over gloo on the CPU and on
+        virtual ranks (ThreadComm) on one GPU; its wire time is unmeasured."""
         if isinstance(max_key_slots, bool) or not isinstance(max_key_slots, int) or not 32 <= max_key_slots <= 128:
             raise ValueError(f"max_key_slots must be an integer in 32 .. 128, got {max_key_slots!r}")
         self.max_key_slots = max_key_slots
+        self.window_keys = bool(window_keys)
+        self.window_p2p = True      # the window exchange by batched p2p + one broadcast (else: gather_frames + row copies)
+        self._wplans, self._wplan = {}, None
         self.lay, self.comm = layout, comm
         self.T_full, self.T_loc, self.f0, self.f1 = layout.T, layout.T_loc, layout.f0, layout.f1
         self.p2p = p2p
@@ -359,6 +410,36 @@ class FrameParallel:
         if float(flag.item()) < len(grp):
             self.kv_inplace = False
             report["kv_gather"] = "compacting all_gather (the in-place path failed its self-check)"
+        # --- window exchange (window_keys): the neighbours' blocks and shard 0's anchor frames against the same all_gather
+        if self.window_keys:
+            short = min(b - a for a, b in lay.bounds)
+            try:
+                keep = self._wplan
+                plan = self.window_plan(min(2, short), min(1, short))
+            except ValueError:                              # (the same on every rank: the rules read the layout alone)
+                plan = None
+                report["window"] = "not checked (no window fits this layout)"
+            if plan is not None:
+                ok = 1.0
+                try:
+                    clip = torch.cat([ref[s_][:(b - a) * rows] for s_, (a, b) in enumerate(lay.bounds)], 0)
+                    buf, own = self.window_buffer(rows, C, device)
+                    buf.zero_()
+                    own.copy_(mine)
+                    self.window_begin(buf, rows).wait()
+                    na = plan.anchor * rows
+                    if not torch.equal(buf[:na], clip[:na]) or not torch.equal(buf[na:], clip[plan.b0 * rows:plan.b1 * rows]):
+                        ok = 0.0
+                except Exception as e:  # noqa: BLE001
+                    ok = 0.0
+                    report["window_error"] = repr(e)[:200]
+                self._wplan = keep
+                flag = torch.tensor([ok], dtype=torch.float64, device=device)
+                self.comm.all_reduce_sum(flag, grp)
+                report["window"] = "batched p2p + anchor broadcast"
+                if float(flag.item()) < len(grp):
+                    self.window_p2p = False
+                    report["window"] = "gather_frames + row copies (the p2p window exchange failed its self-check)"
         # --- halo path
         if self.p2p:
             ok = 1.0
@@ -504,6 +585,82 @@ class FrameParallel:
             self.log.append((self.lane, "tokens"))
         return self.comm.all_gather_into(buf, self.lay.T_max * rows_per_frame, self.lay.frame_group, lane=self.lane)
 
+    # windowed temporal attention (window_keys) ---------------------------------------------------------------------
+    def window_plan(self, radius, anchor):
+        """What this rank's temporal attention needs under the window (radius, anchor); pure Python, no communicator.  ->
+        a namespace: b0 = max(f0 - radius, 0), b1 = min(f1 + radius, T_full) (the band frames [b0, b1)), S = anchor + b1 - b0 key
+        slots (anchor slots first), own = anchor + f0 - b0 (the slot of this rank's first frame), send_prev / send_next /
+        recv_prev / recv_next (frames to and from each neighbour), recv_anchor (anchor frames taken from shard 0),
+        frames_window = what this rank receives per temporal layer on this path, frames_gathered = what it receives from the
+        in-place token gather ((frame_ranks - 1) x T_max slots, padding included).  Three rules keep the exchange to the
+        immediate neighbours and one source of anchors; ValueError names the one that fails.  The plan is kept for
+        ``window_buffer`` / ``window_begin``."""
+        import types
+        if not self.window_keys:
+            raise ValueError("window_plan: this parallel object was built without window_keys=True")
+        lay = self.lay
+        radius, anchor = int(radius), int(anchor)
+        if radius < 0 or anchor < 0:
+            raise ValueError(f"window_plan: radius {radius} and anchor {anchor} must be >= 0")
+        key = (radius, anchor)
+        plan = self._wplans.get(key)
+        if plan is None:
+            radius = min(radius, lay.T - 1)                   # (a larger radius sees the same frames)
+            short, first = min(b - a for a, b in lay.bounds), lay.bounds[0][1] - lay.bounds[0][0]
+            if lay.frame_ranks > 1 and radius > short:
+                raise ValueError(f"window_plan: radius {radius} exceeds the smallest frame shard ({short} of {lay.T} frames over "
+                                 f"{lay.frame_ranks} shards): the band would reach beyond the neighbour shard")
+            if anchor > first:
+                raise ValueError(f"window_plan: anchor {anchor} exceeds the {first} frames of shard 0: the anchor frames would come "
+                                 "from more than one shard")
+            if anchor + lay.T_max + 2 * radius > 128:
+                raise ValueError(f"window_plan: anchor + T_max + 2 radius = {anchor} + {lay.T_max} + 2 x {radius} = "
+                                 f"{anchor + lay.T_max + 2 * radius} key slots exceed the attention kernel's 128")
+            b0, b1 = max(self.f0 - radius, 0), min(self.f1 + radius, lay.T)
+            p = types.SimpleNamespace(radius=radius, anchor=anchor, b0=b0, b1=b1, S=anchor + b1 - b0, own=anchor + self.f0 - b0)
+            p.recv_prev, p.recv_next = self.f0 - b0, b1 - self.f1
+            p.send_prev = radius if lay.shard > 0 else 0      # (what the neighbour's own plan receives: its band ends radius
+            p.send_next = radius if lay.shard + 1 < lay.frame_ranks else 0   # frames inside this shard, radius <= every shard)
+            p.recv_anchor = anchor if lay.shard > 0 else 0
+            p.frames_window = p.recv_prev + p.recv_next + p.recv_anchor
+            p.frames_gathered = (lay.frame_ranks - 1) * lay.T_max
+            plan = self._wplans[key] = p
+        self._wplan = plan
+        return plan
+
+    def window_buffer(self, rows_per_frame, C, device):
+        """-> (buf [S * rows, C] uninitialised, own [T_loc * rows, C] = this rank's frames inside its band) for the plan
+        ``window_plan`` made last: the LayerNorm writes ``own`` in place, ``window_begin`` fills the rest"""
+        p = self._wplan
+        if p is None:
+            raise ValueError("window_buffer: call window_plan(radius, anchor) first")
+        buf = torch.empty((p.S * rows_per_frame, C), dtype=torch.float16, device=device)
+        return buf, buf[p.own * rows_per_frame:(p.own + self.T_loc) * rows_per_frame]
+
+    def window_begin(self, buf, rows_per_frame):
+        """Starts the exchange that completes ``buf`` (of ``window_buffer``, own frames written): ``wait()`` leaves every slot in
+        place in stream order.  Fast path: ``radius`` frames to and from each neighbour by batched p2p on the lane's "data"
+        communicator, received into their slots, and the anchor frames broadcast from shard 0 (which copies them from its own
+        band) on the lane's bulk communicator.  Conservative path (the fast one failed ``self_check``): ``gather_frames`` of the
+        own frames, then row copies of the anchor and band frames -- the same rows in the same slots, so the same bits."""
+        p, lay, n = self._wplan, self.lay, rows_per_frame
+        if p is None:
+            raise ValueError("window_begin: call window_plan(radius, anchor) first")
+        if self.log is not None:
+            self.log.append((self.lane, "window"))
+        own = buf[p.own * n:(p.own + self.T_loc) * n]
+        if not self.window_p2p:
+            clip = self.gather_frames(own, n)
+            buf[:p.anchor * n].copy_(clip[:p.anchor * n])
+            buf[p.anchor * n:].copy_(clip[p.b0 * n:p.b1 * n])
+            return _Done()
+        rows = lambda a, b: buf[a * n:b * n] if b > a else None            # noqa: E731
+        if lay.shard == 0 and p.anchor:
+            buf[:p.anchor * n].copy_(buf[p.own * n:(p.own + p.anchor) * n])     # (b0 = 0: the band starts at frame 0)
+        return self.comm.window_begin(rows(p.own, p.own + p.send_prev), rows(p.own + self.T_loc - p.send_next, p.own + self.T_loc),
+                                      rows(p.anchor, p.anchor + p.recv_prev), rows(p.S - p.recv_next, p.S),
+                                      lay.prev_rank, lay.next_rank, rows(0, p.anchor), lay.frame_group, lane=self.lane)
+
     def gather_frames(self, t, rows_per_frame):
         """t [T_loc*rows, C] (this shard's frames) -> [T_full*rows, C] in frame order (uneven shards are padded to
         the largest for the collective and compacted afterwards)."""
@@ -536,13 +693,15 @@ class GroupedWindowParallel:
     hands every rank every stepped window (the g ranks of a group hold identical copies; entry 0 of each group is used).
     ``window_layout_costs`` says when this beats the two plain layouts (e.g. 4 windows on 8 ranks: 4 x 2)."""
 
-    def __init__(self, comm, rank, world, ranks_per_group, window_size, max_key_slots=32):
+    def __init__(self, comm, rank, world, ranks_per_group, window_size, max_key_slots=32, window_keys=False):
         g = ranks_per_group
         assert world % g == 0 and g >= 2 and g % 2 == 0
         self.comm, self.rank, self.world, self.g = comm, rank, world, g
         self.groups, self.slot = world // g, rank // g
-        self.frame = FrameParallel(Layout(g, rank % g, window_size, base=self.slot * g), comm, max_key_slots=max_key_slots)
+        self.frame = FrameParallel(Layout(g, rank % g, window_size, base=self.slot * g), comm, max_key_slots=max_key_slots,
+                                   window_keys=window_keys)
         self.max_key_slots = self.frame.max_key_slots               # (what pipeline._check_call asks a ``parallel`` object for)
+        self.window_keys = self.frame.window_keys
 
     @staticmethod
     def layout_of_rank(world, ranks_per_group, window_size):

@@ -183,8 +183,13 @@ class FlowControlNetPipeline:
         anchor): local temporal attention in every temporal layer of the UNet and the adapters -- query frame i sees key
         frame j iff j < anchor or |i - j| <= radius (mofa_attn_temporal_long_local_f16); an integer means (radius, 1), frame 0
         being the conditioning frame.  In the Keypoint window loop the rule applies inside every window (a window is one
-        forward pass of window_size frames).  Not available with a ``parallel`` object that shards frames.  Nothing is claimed
-        about what the released checkpoints produce under it."""
+        forward pass of window_size frames).  With a ``parallel`` object that shards frames it needs one built with
+        ``window_keys=True``: every rank then exchanges ``radius`` frames with its neighbour shards and takes the anchor frames
+        from shard 0 instead of gathering the clip, and attends through mofa_attn_temporal_long_window_f16.  The key slots of a
+        rank, anchor + largest shard + 2 radius <= 128, then take the place of ``max_key_slots`` (``FrameParallel.window_plan``
+        names the rule a layout breaks); ``max_temporal_frames`` still caps the frames of a forward pass.  That path has been
+        checked over gloo on the CPU and on virtual ranks on one GPU; nothing was run on more than one GPU.  Nothing is
+        claimed about what the released checkpoints produce under a window."""
         self.temporal_window = _temporal_window(temporal_window)
         streams = self.temporal_window is not None and self.temporal_window[0] <= STREAM_RADIUS \
             and self.temporal_window[1] <= STREAM_ANCHOR
@@ -350,10 +355,13 @@ class FlowControlNetPipeline:
                              "own forward accepts: its controlnet_condition / added_time_ids are not repeated)")
         if not max_guidance_scale > 1.0:
             raise ValueError("the reference pipeline is only well-defined with classifier-free guidance on")
+        windowed_shards = False
         if self.temporal_window is not None:
             if _shards_frames(self.parallel):
-                raise ValueError("temporal_window=... with a parallel object that shards frames: the gathered-key path of "
-                                 "frame-sharded clips has no per-query mask (a CFG split alone and WindowParallel are fine)")
+                if not getattr(self.parallel, "window_keys", False):
+                    raise ValueError("temporal_window=... with a parallel object that shards frames: the gathered-key path of "
+                                     "frame-sharded clips has no per-query mask (a CFG split alone and WindowParallel are fine)")
+                windowed_shards = True          # built with window_keys=True: band + anchor keys, checked below
             if self.temporal_window[1] > frames_per_forward:
                 raise ValueError(f"temporal_window anchor {self.temporal_window[1]} exceeds the {frames_per_forward} frames of a "
                                  "forward pass")
@@ -363,7 +371,14 @@ class FlowControlNetPipeline:
                              f"{limit} (use KeypointFlowControlNetPipeline's window loop for long clips"
                              + (f", or build the pipeline with max_temporal_frames=... up to {MAX_TEMPORAL_FRAMES_LONG})"
                                 if limit < MAX_TEMPORAL_FRAMES_LONG else ")"))
-        if self.parallel is not None:
+        if windowed_shards:
+            # the key slots of a rank (anchor + largest shard + 2 radius <= 128) replace max_key_slots; window_plan names the
+            # rule a layout breaks.  The same verdict on every rank: the rules read the layout alone
+            fpar = getattr(self.parallel, "frame", self.parallel)
+            if fpar.lay.T != frames_per_forward:
+                raise ValueError(f"{frames_per_forward} frames per forward pass, but the parallel object's layout shards {fpar.lay.T}")
+            fpar.window_plan(*self.temporal_window)
+        elif self.parallel is not None:
             slots = getattr(self.parallel, "max_key_slots", MAX_TEMPORAL_FRAMES)
             if frames_per_forward > slots and slots == MAX_TEMPORAL_FRAMES:
                 raise ValueError(f"{frames_per_forward} frames per forward pass with parallel=...: clips sharded over ranks are limited "
