@@ -428,7 +428,12 @@ int mofa_timestep_embedding(const float* t, float* out, int n, int dim, mofa_str
  *   feat : fp16 token-major [HW][ldf]      (first-frame feature, one image)
  *   flow : fp32 [nflows][2][H][W]          (flow frame 0 -> frame i+1 at feature resolution)
  *   out  : fp16 token-major [nflows][HW][ldo]
- *   ws   : int32/fp32 workspace, mofa_softsplat_ws_bytes(nflows, H, W) bytes
+ *   ws   : int32/fp32 workspace, mofa_softsplat_ws_bytes(nflows, H, W) bytes (formed in 64 bits), cleared by every call:
+ *          what it held before does not matter, and nothing beyond that size is touched
+ * Limits of mofa_softsplat_avg_f16, checked before any device call (MOFA_EINVAL): no NULL pointer; 1 <= nflows <= 65535 (a grid
+ * dimension); H, W >= 1 and H * W < 2^29 (the CSR keys corner * HW + source are int; the product is formed in 64 bits); C >= 8
+ * and a multiple of 8; ldf and ldo multiples of 8.  A source whose target x + flow is not finite is skipped; a finite target
+ * however far outside the plane (beyond the int range included) contributes to no pixel.
  * mofa_softsplat_scatter_f32 is the atomicAdd form of the reference kernel on NCHW fp32
  * (same op order class as the CUDA kernel; used for parity classing and as a bench baseline).
  * ---------------------------------------------------------------------------------------- */

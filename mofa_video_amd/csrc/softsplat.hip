@@ -22,6 +22,11 @@ struct Corners {
     float w[4];
 };
 
+// floor of a finite coordinate, kept within +-2^30: converting a float beyond the int range to int is undefined, and so is
+// x0 + 1 at INT_MAX.  A plane has fewer than 2^29 pixels, so every corner of such a source is out of bounds before and after
+// the clamp, and no coordinate within +-2^30 changes.
+__device__ __forceinline__ float ss_floor(float f) { return fminf(fmaxf(floorf(f), -1073741824.0f), 1073741824.0f); }
+
 // softsplat.py:298-334
 __device__ __forceinline__ bool splat_corners(const float* __restrict__ flow, int s, int H, int W, Corners& c) {
     const int HW = H * W;
@@ -29,7 +34,7 @@ __device__ __forceinline__ bool splat_corners(const float* __restrict__ flow, in
     const float fx = (float)x + flow[s];
     const float fy = (float)y + flow[HW + s];
     if (!isfinite(fx) || !isfinite(fy)) return false;
-    const float flx = floorf(fx), fly = floorf(fy);
+    const float flx = ss_floor(fx), fly = ss_floor(fy);
     const int x0 = (int)flx, y0 = (int)fly;
     const float x1f = (float)(x0 + 1), y1f = (float)(y0 + 1), x0f = (float)x0, y0f = (float)y0;
     c.w[0] = (x1f - fx) * (y1f - fy);  // NW
@@ -45,10 +50,13 @@ __device__ __forceinline__ bool splat_corners(const float* __restrict__ flow, in
 }
 
 // workspace per flow frame: count[HW] | offset[HW+1] | cursor[HW] | keys[4HW] | wts[4HW]
-static inline int64_t ws_ints_per_flow(int HW) { return (int64_t)HW * 3 + 1 + (int64_t)HW * 8; }
+static inline int64_t ws_ints_per_flow(int64_t HW) { return HW * 3 + 1 + HW * 8; }
 extern "C" int64_t mofa_softsplat_ws_bytes(int nflows, int H, int W) {
-    return ws_ints_per_flow(H * W) * 4 * (int64_t)nflows + 64;
+    return ws_ints_per_flow((int64_t)H * W) * 4 * (int64_t)nflows + 64;
 }
+
+// one image plane holds fewer than 2^29 pixels: the CSR keys corner * HW + source are int
+static bool ss_plane_ok(int H, int W) { return H > 0 && W > 0 && (int64_t)H * W < (1LL << 29); }
 
 __global__ void ss_count_kernel(const float* __restrict__ flow, int* __restrict__ ws, int H, int W, long long per) {
     const int HW = H * W, i = blockIdx.y;
@@ -217,11 +225,18 @@ static int ss_build_csr(const float* flow, void* ws, int nflows, int H, int W, h
     return MOFA_OK;
 }
 
+// the argument rules of mofa_softsplat_avg_f16 (include/mofa_hip.h), host arithmetic only: nflows is a grid dimension
+static int ss_avg_check(const void* feat, const float* flow, const void* out, const void* ws, int nflows, int H, int W, int C,
+                        int ldf, int ldo) {
+    if (!feat || !flow || !out || !ws || nflows <= 0 || nflows > 65535 || !ss_plane_ok(H, W) || C <= 0 || C % 8 != 0 ||
+        ldf % 8 != 0 || ldo % 8 != 0)
+        return MOFA_EINVAL;
+    return MOFA_OK;
+}
+
 extern "C" int mofa_softsplat_avg_f16(const void* feat, const float* flow, void* out, void* ws, int nflows, int H, int W,
                                       int C, int ldf, int ldo, mofa_stream_t stream) {
-    if (!feat || !flow || !out || !ws || nflows <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || ldf % 8 != 0 ||
-        ldo % 8 != 0)
-        return MOFA_EINVAL;
+    if (ss_avg_check(feat, flow, out, ws, nflows, H, W, C, ldf, ldo) != MOFA_OK) return MOFA_EINVAL;
     const int HW = H * W;
     const long long per = ws_ints_per_flow(HW);
     hipStream_t st = (hipStream_t)stream;
@@ -329,7 +344,6 @@ __global__ void ss_norm_kernel(const int* __restrict__ ws, float* __restrict__ n
     for (int j = a; j < b; ++j) s += wts[j];
     norm[(size_t)i * HW + t] = s;
 }
-static bool ss_plane_ok(int H, int W) { return H > 0 && W > 0 && (int64_t)H * W < (1LL << 29); }
 
 extern "C" int mofa_softsplat_norm_f32(const float* flow, float* norm, void* ws, int N, int H, int W, mofa_stream_t stream) {
     if (!flow || !norm || !ws || N <= 0 || N > 65535 || !ss_plane_ok(H, W)) return MOFA_EINVAL;
@@ -393,7 +407,7 @@ __device__ __forceinline__ bool splat_corners_grad(const float* __restrict__ flo
     const int y = s / W, x = s - y * W;
     const float fx = (float)x + flow[s];
     const float fy = (float)y + flow[H * W + s];
-    const float x0f = floorf(fx), y0f = floorf(fy);
+    const float x0f = ss_floor(fx), y0f = ss_floor(fy);
     const float x1f = (float)((int)x0f + 1), y1f = (float)((int)y0f + 1);
     dx[0] = -(y1f - fy); dx[1] = y1f - fy; dx[2] = -(fy - y0f); dx[3] = fy - y0f;
     dy[0] = -(x1f - fx); dy[1] = -(fx - x0f); dy[2] = x1f - fx; dy[3] = fx - x0f;
