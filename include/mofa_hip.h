@@ -548,14 +548,20 @@ int mofa_step_select(const float* table, int* counter, float* cur, int nsteps, m
 /* ---- output stage (the step after the path) -------------------------------------------------------------
  * Replaces tensor2vid -> VaeImageProcessor.postprocess (Traj/pipeline/pipeline.py:57-69, :518): decoded fp32 frames
  * [nframes][3][H][W] -> (x/2+0.5).clamp(0,1) as fp32 NCHW ("pt"), fp32 NHWC ("np") or uint8 NHWC ("pil":
- * round-half-even(x*255)). */
+ * round-half-even(x*255)).  A NaN input stays NaN in the two float modes, as torch's clamp propagates it (a broken decode
+ * must not come out as clean black frames); the uint8 mode, which has no NaN, writes 0 for it.  +-inf clamp to 1 / 0. */
 #define MOFA_FRAMES_PT 0
 #define MOFA_FRAMES_NP 1
 #define MOFA_FRAMES_U8 2
 int mofa_frames_postprocess_f32(const float* frames_nchw, void* out, int nframes, int H, int W, int mode,
                                 mofa_stream_t stream);
 /* Middlebury colour coding of one flow field, fp32 [H][W][2] -> uint8 [H][W][3]; replaces flow_to_image
- * (Traj/utils/flow_viz.py:241-277 with compute_color :196-238).  workspace: mofa_flow_to_image_ws_bytes(H, W). */
+ * (Traj/utils/flow_viz.py:241-277 with compute_color :196-238).  workspace: mofa_flow_to_image_ws_bytes(H, W).
+ * A pixel with a component beyond 1e7 in magnitude (exactly 1e7 is not) is unknown: black, and left out of the maximum
+ * radius that scales the picture.  A pixel with a NaN component is treated the same way: black, excluded from the maximum,
+ * and every other pixel is as if it held zero flow.  This deliberately does not copy the reference's accident: there
+ * compute_color also blackens the pixel, but max(-1, nan) makes the maximum -1, which negates and rescales all the others.
+ * The maximum is sqrt(u*u + v*v) with every operation rounded to fp32 on its own, as torch computes it. */
 int64_t mofa_flow_to_image_ws_bytes(int H, int W);
 int mofa_flow_to_image_u8(const float* flow_hw2, unsigned char* out_hw3, int H, int W, void* workspace,
                           mofa_stream_t stream);

@@ -3,10 +3,16 @@
 //     (Traj/pipeline/pipeline.py:57-69, :518): denormalise (x / 2 + 0.5).clamp(0, 1), then keep NCHW fp32 ("pt"),
 //     or NHWC fp32 ("np"), or NHWC uint8 = round-half-even(x * 255) ("pil", numpy's .round()).
 //   * flow_to_image: the Middlebury colour coding of a flow field the reference's UIs display
-//     (Traj/utils/flow_viz.py:196-277): unknown (> 1e7) entries zeroed, both components divided by (max radius + eps),
+//     (Traj/utils/flow_viz.py:196-277): unknown (> 1e7, or NaN) entries zeroed, both components divided by (max radius + eps),
 //     colour-wheel interpolation on the angle, saturation by the radius, in fp64 as numpy computes it.
 // HBM-bound elementwise kernels; the flow maximum is a two-step reduction (per-block maxima, then one block).
 #include "common.h"
+
+// torch and numpy round every operation on its own.  hipcc contracts a * b + c into one fma by default, and calls of
+// __fmul_rn / __fadd_rn are no protection (plain operators in the HIP headers, compiled under the default): a fused
+// u*u + v*v moved the radius and the maximum by an ulp, which flipped bytes where 255 * col sits on an integer and missed
+// compute_color's rad > 1 branch at the maximum pixel.  So: contraction off for this file, plain operators in the kernels.
+#pragma clang fp contract(off)
 
 __global__ __launch_bounds__(256) void frames_postprocess_kernel(const float* __restrict__ x, void* __restrict__ out,
                                                                  const long long npix, const int HW, const int mode) {
@@ -18,7 +24,8 @@ __global__ __launch_bounds__(256) void frames_postprocess_kernel(const float* __
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float t = x[(f * 3 + c) * HW + p] * 0.5f + 0.5f;   // x / 2 is exact, so this equals (x / 2 + 0.5) in fp32
-        v[c] = fminf(fmaxf(t, 0.0f), 1.0f);
+        const float cl = fminf(fmaxf(t, 0.0f), 1.0f);            // fmaxf(NaN, 0) = 0: the uint8 mode's 0 for a NaN
+        v[c] = (mode != MOFA_FRAMES_U8 && t != t) ? t : cl;      // torch's clamp propagates NaN: the float modes keep it
     }
     if (mode == MOFA_FRAMES_PT) {
         float* o = (float*)out;
@@ -46,9 +53,13 @@ extern "C" int mofa_frames_postprocess_f32(const float* frames_nchw, void* out, 
 
 // ---- flow visualisation ---------------------------------------------------------------------------------------------
 #define FLOW_UNKNOWN 1e7f
+// unknown: a component beyond 1e7 in magnitude (exactly 1e7 is known) or NaN -- black, and no part of the maximum
+__device__ __forceinline__ bool flow_unknown(const float u, const float v) {
+    return !(fabsf(u) <= FLOW_UNKNOWN) || !(fabsf(v) <= FLOW_UNKNOWN);
+}
 __device__ __forceinline__ void flow_uv(const float* flow, long long i, float& u, float& v) {
     u = flow[2 * i]; v = flow[2 * i + 1];
-    if (fabsf(u) > FLOW_UNKNOWN || fabsf(v) > FLOW_UNKNOWN) { u = 0.0f; v = 0.0f; }
+    if (flow_unknown(u, v)) { u = 0.0f; v = 0.0f; }
 }
 
 __global__ __launch_bounds__(256) void flow_maxrad_kernel(const float* __restrict__ flow, float* __restrict__ part,
@@ -59,7 +70,7 @@ __global__ __launch_bounds__(256) void flow_maxrad_kernel(const float* __restric
         if (final_pass) { m = fmaxf(m, flow[i]); continue; }
         float u, v;
         flow_uv(flow, i, u, v);
-        m = fmaxf(m, sqrtf(u * u + v * v));                 // torch.sqrt(u**2 + v**2) in fp32
+        m = fmaxf(m, sqrtf(u * u + v * v));                 // torch.sqrt(u**2 + v**2) in fp32, unfused (pragma above)
     }
     m = wave_max(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
@@ -85,7 +96,7 @@ __global__ __launch_bounds__(256) void flow_to_image_kernel(const float* __restr
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float fu = flow[2 * i], fv = flow[2 * i + 1];
-    const bool unknown = fabsf(fu) > FLOW_UNKNOWN || fabsf(fv) > FLOW_UNKNOWN;
+    const bool unknown = flow_unknown(fu, fv);
     // u / (maxrad + eps): torch divides the fp32 tensor by a python float -> fp32 result
     const float den = (float)((double)maxrad[0] + 2.220446049250313e-16);
     const double u = unknown ? 0.0 : (double)(fu / den), v = unknown ? 0.0 : (double)(fv / den);
@@ -93,9 +104,10 @@ __global__ __launch_bounds__(256) void flow_to_image_kernel(const float* __restr
     // numpy keeps these in fp32 (fp32 arrays combined with python scalars): rad, arctan2 / pi, fk; f = fk - k0 and the
     // colour interpolation are fp64 (int64 / fp64 operands)
     const float uf = (float)u, vf = (float)v;
-    const float rad = sqrtf(__fadd_rn(__fmul_rn(uf, uf), __fmul_rn(vf, vf)));
-    const float a = __fdiv_rn(atan2f(-vf, -uf), 3.14159274101257324f);
-    const float fk = __fadd_rn(__fmul_rn(__fdiv_rn(__fadd_rn(a, 1.0f), 2.0f), (float)(ncols - 1)), 1.0f);
+    // plain operators, each rounded on its own under the pragma above (the __f*_rn intrinsics do not keep hipcc from fusing)
+    const float rad = sqrtf(uf * uf + vf * vf);
+    const float a = atan2f(-vf, -uf) / 3.14159274101257324f;
+    const float fk = (a + 1.0f) / 2.0f * (float)(ncols - 1) + 1.0f;
     const int k0 = (int)floorf(fk);
     int k1 = k0 + 1;
     if (k1 == ncols + 1) k1 = 1;

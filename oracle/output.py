@@ -84,7 +84,10 @@ def flow_to_image(flow: torch.Tensor):                         # flow_viz.py:241
     unknown = (abs(u) > UNKNOWN_FLOW_THRESH) | (abs(v) > UNKNOWN_FLOW_THRESH)
     u[unknown] = 0
     v[unknown] = 0
-    rad = torch.sqrt(u ** 2 + v ** 2)
+    # torch.sqrt on the CPU may go through a vector maths library whose result depends on the host processor (seen an ulp
+    # off the correctly rounded root on one machine and exact on another); numpy's is the correctly rounded one everywhere,
+    # as is the sqrt of the GPU the reference runs this line on
+    rad = torch.from_numpy(np.sqrt((u ** 2 + v ** 2).cpu().numpy()))
     maxrad = max(-1, torch.max(rad).cpu().numpy())
     u = u / (maxrad + np.finfo(float).eps)
     v = v / (maxrad + np.finfo(float).eps)
