@@ -354,6 +354,354 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const f16* __restr
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// attn_spatial_q64_kernel: the D = 64, QB = 2 case (64 queries per wave; the level-0 / level-1 launches of a clip) with its
+// key-tile schedule laid out by hand.  Grid, XCD-aware work order, LDS image (two buffers, the swizzles above), DMA pieces,
+// one barrier per tile, the reference rule and -- per query row -- the sequence of MFMAs, v_exp_f32, adds and fp16 roundings are
+// those of attn_spatial_kernel<64, 2>: the output is bit-identical.  What differs is what a wave issues around them:
+//   * tile 0 (always moves the reference) and a ragged last tile (key mask) run the straight code of the template OUTSIDE the
+//     loop; the loop body has neither test.  It is unrolled over the two buffers, so every K / V^T fragment is read at
+//     base + immediate (4 + 2 address registers for the whole kernel) and the DMA destinations are wave base + immediate in M0
+//     (wave index made uniform once).
+//   * fragment read-ahead: K fragments are read ATT_Q64_KAHEAD MFMA pairs ahead of their use, the first ones of the next tile
+//     right after the barrier; V^T fragments one group of four transpose reads ahead, the first group before the softmax of
+//     query block 1; the compiler counts the waits (lgkmcnt(n)).  sched_barrier after every MFMA pair and every eight
+//     probabilities keeps that order (without them hipcc regroups the reads: - 1.5 %).
+//   * the reference check is lane-local on the common path (no shuffle, no LDS round trip in front of the branch), see the
+//     comment at the check.
+//   * O leaves through the LDS as whole 128-byte rows.
+// Measured and dropped (profiles/attn_spatial_sched_bench.log): the exp / add / pack of key half 0 beside the S^T MFMAs of
+// key half 1 (- 1.4 %: with two waves per SIMD the partner wave's MFMAs already fill the softmax), three K fragments ahead,
+// pinning each P fragment's pack to its eight probabilities, the DMA of tile 0 in front of the Q loads.
+constexpr int ATT_Q64_KAHEAD = 2;
+template <int V> struct AttIC { static constexpr int v = V; };
+
+__global__ __launch_bounds__(256, 2) void attn_spatial_q64_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                  const f16* __restrict__ v, f16* __restrict__ out,
+                                                                  int heads, int S, int ldq, int ldk, int ldv, int ldo, float c,
+                                                                  int nqb, int total) {
+    constexpr int D = 64, KK = 4, DB = 2;
+    constexpr int TILE_B = ATT_TILE * D * 2;             // bytes of one K (or V) tile image
+    constexpr int V_B = 2 * TILE_B;                      // V buffers behind the two K buffers
+    extern __shared__ __attribute__((aligned(16))) char smem_att[];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, lh = lane >> 5;
+    int head, frame, qb_;                                 // (the work order of attn_spatial_kernel)
+    {
+        const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3, qn = total >> 3, rn = total & 7;
+        const int start = xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn;
+        if (local >= qn + (xcd < rn ? 1 : 0)) return;
+        const int w = start + local, pair = w / nqb;
+        qb_ = w - pair * nqb;
+        frame = pair / heads;
+        head = pair - frame * heads;
+    }
+    const int q0 = qb_ * 256 + wave * 64;
+    const f16* kbase = k + (size_t)frame * S * ldk + head * D;
+    const f16* vbase = v + (size_t)frame * S * ldv + head * D;
+
+    // ---- LDS-DMA: descriptors over this (frame, head)'s K / V rows; instruction i of this wave brings tile rows
+    //      (2 wave + i) * 8 + lane / 8 to the lane-linear kilobyte (2 wave + i) of the tile image ----
+    const auto rsk = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, (unsigned)(((size_t)(S - 1) * ldk + D) * 2), 0x00020000);
+    const auto rsv = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, 0, (unsigned)(((size_t)(S - 1) * ldv + D) * 2), 0x00020000);
+    unsigned dko[2], dvo[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = (2 * wave + i) * 8 + (lane >> 3), slot = lane & 7;
+        dko[i] = (unsigned)row * (unsigned)ldk * 2u + (unsigned)((slot ^ ((row >> 1) & 7)) * 16);
+        dvo[i] = (unsigned)row * (unsigned)ldv * 2u + (unsigned)((slot ^ (4 * ((row >> 1) & 1))) * 16);
+    }
+    char* const dma_base = smem_att + wave * 2048;        // wave-uniform: the destinations are this + immediate
+    auto dma_tile = [&](int t, int buf_bytes) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsk, (__attribute__((address_space(3))) void*)(dma_base + buf_bytes + i * 1024),
+                                                     16, dko[i], t * ATT_TILE * ldk * 2, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsv, (__attribute__((address_space(3))) void*)(dma_base + V_B + buf_bytes + i * 1024),
+                                                     16, dvo[i], t * ATT_TILE * ldv * 2, 0, 0);
+        }
+    };
+    const int ntiles = (S + ATT_TILE - 1) / ATT_TILE;
+
+    // Q fragments (B operand of S^T): lane (query l31, half lh) holds Q[q][16*kk + 8*lh .. +8), times c unless c == 1
+    f16x8 qf[2][KK];
+    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int qi = q0 + b * 32 + l31;
+        const f16* qp = q + ((size_t)frame * S + (qi < S ? qi : 0)) * ldq + head * D + lh * 8;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+            const f16x8 v = (qi < S) ? *(const f16x8*)(qp + kk * 16) : zero8;
+            qf[b][kk] = v;
+            if (c != 1.0f) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) qf[b][kk][e] = (f16)((float)v[e] * c);
+            }
+        }
+    }
+
+    f32x16 o[2][DB];
+    f32x16 negm[2];                                       // -m_run[b] in all 16 registers: the C operand of every S^T chain
+    float l_run[2];                                       // (the reference m_run[b] is -negm[b][0])
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) negm[b][r] = 0.f;
+        l_run[b] = 0.f;
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[b][db][r] = 0.f;
+    }
+
+    // fragment addresses (bytes, buffer 0): K fragment (ts, kk) at kaddr[kk] + ts * 4096, V^T pieces at vaddr[db] + key row * 128
+    const int ksw = (l31 >> 1) & 7, vsw = (lane >> 3) & 1;
+    int kaddr[KK], vaddr[DB];
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk) kaddr[kk] = l31 * (D * 2) + ((2 * kk + lh) ^ ksw) * 16;
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+        vaddr[db] = V_B + 2 * ((((lane & 15) >> 2) + 4 * lh) * D + 16 * ((lane >> 4) & 1) + 4 * (lane & 3) + (db ^ vsw) * 32);
+    auto k_frag = [&](int buf_bytes, int i) __attribute__((always_inline)) {     // i = 4 ts + kk
+        return *(const f16x8*)(smem_att + kaddr[i & 3] + buf_bytes + (i >> 2) * 4096);
+    };
+    auto v_frag = [&](int buf_bytes, int j) __attribute__((always_inline)) {     // j = 4 db + 2 ts + u
+        const char* vp = smem_att + vaddr[j >> 2] + buf_bytes + (((j >> 1) & 1) * 32 + (j & 1) * 16) * (D * 2);
+        const f16x4 lo = lds_read_tr4((const f16*)vp);                            // keys k0 + 4 lh + 0..3
+        const f16x4 hi = lds_read_tr4((const f16*)(vp + 8 * D * 2));              // keys k0 + 4 lh + 8..11
+        return f16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    };
+
+    // N probabilities (registers r0 .. r0 + N - 1 of one S^T tile, inside one P fragment): exp2 of the accumulators as they
+    // are, summed in key order, packed; a key half of a query block is registers 0 .. 15 in this order
+    auto soft_piece = [&](const f32x16& sv, auto r0c, auto nc, float& psum, f16x8 (&pf)[2]) __attribute__((always_inline)) {
+        constexpr int R0 = decltype(r0c)::v, N = decltype(nc)::v;
+#pragma unroll
+        for (int r = R0; r < R0 + N; ++r) {
+            const float p = __builtin_amdgcn_exp2f(sv[r]);
+            psum += p;
+            pf[r >> 3][r & 7] = (f16)p;
+        }
+    };
+    auto soft_half = [&](const f32x16& sv, float& psum, f16x8 (&pf)[2]) __attribute__((always_inline)) {
+        soft_piece(sv, AttIC<0>{}, AttIC<16>{}, psum, pf);
+    };
+    // the reference rule of attn_spatial_kernel for query block b, given the lane's half sum; first = tile 0
+    auto reference_rule = [&](int b, f32x16 (&s)[2][2], float& psum, f16x8 (&pf)[2][2][2], bool first) __attribute__((always_inline)) {
+        const float ptot = psum + __shfl_xor(psum, 32, 64);               // both key halves of the query row
+        const bool move = !(ptot < ATT_DEFER_SUM) || first;               // (NaN-safe)
+        if (__any(move)) {
+            asm volatile("; reference moves" ::: "memory");
+            float mx = s[b][0][0];
+#pragma unroll
+            for (int ts = 0; ts < 2; ++ts)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[b][ts][r]);
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float delta = move ? mx : 0.f;
+            const float alpha = __builtin_amdgcn_exp2f(-delta);
+            const float m_new = -negm[b][0] + delta;                       // m_run[b] += delta
+#pragma unroll
+            for (int r = 0; r < 16; ++r) negm[b][r] = -m_new;
+            l_run[b] *= alpha;
+#pragma unroll
+            for (int db = 0; db < DB; ++db)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[b][db][r] *= alpha;
+            psum = 0.f;
+#pragma unroll
+            for (int ts = 0; ts < 2; ++ts)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float p = __builtin_amdgcn_exp2f(s[b][ts][r] - delta);
+                    psum += p;
+                    pf[b][ts][r >> 3][r & 7] = (f16)p;
+                }
+        }
+    };
+
+    // ---- an edge tile (tile 0, a ragged last tile): the straight code of attn_spatial_kernel ----
+    auto edge_tile = [&](int t, int buf_bytes) __attribute__((always_inline)) {
+        const int k0 = t * ATT_TILE;
+        if (t + 1 < ntiles) dma_tile(t + 1, buf_bytes ^ TILE_B);
+        f32x16 s[2][2];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const f16x8 kf = k_frag(buf_bytes, i);
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                s[b][i >> 2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[b][i & 3], (i & 3) == 0 ? negm[b] : s[b][i >> 2], 0, 0, 0);
+        }
+        if (__builtin_amdgcn_readfirstlane(k0 + ATT_TILE > S)) {
+            asm volatile("; tail tile" ::: "memory");
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int ts = 0; ts < 2; ++ts)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int key = k0 + ts * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        if (key >= S) s[b][ts][r] = -1e30f;
+                    }
+        }
+        f16x8 pf[2][2][2];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            float psum = 0.f;
+            soft_half(s[b][0], psum, pf[b][0]);
+            soft_half(s[b][1], psum, pf[b][1]);
+            reference_rule(b, s, psum, pf, t == 0);
+            l_run[b] += psum;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const f16x8 vf = v_frag(buf_bytes, j);
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                o[b][j >> 2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[b][(j >> 1) & 1][j & 1], o[b][j >> 2], 0, 0, 0);
+        }
+        if (t + 1 < ntiles) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    };
+
+    // ---- a tile of the loop: neither the first nor masked; BUF = its buffer, kr = its first K fragments (read after the
+    //      barrier that released the buffer) ----
+    f16x8 kr[ATT_Q64_KAHEAD];
+    auto k_head = [&](int buf_bytes) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < ATT_Q64_KAHEAD; ++i) kr[i] = k_frag(buf_bytes, i);
+    };
+    auto loop_tile = [&](auto bufc, int t) __attribute__((always_inline)) {
+        constexpr int BUF_B = decltype(bufc)::v * TILE_B;
+        if (t + 1 < ntiles) dma_tile(t + 1, BUF_B ^ TILE_B);
+        f32x16 s[2][2];
+        f16x8 pf[2][2][2];
+        float psum[2] = {0.f, 0.f};
+        f16x8 kf[8];
+#pragma unroll
+        for (int i = 0; i < ATT_Q64_KAHEAD; ++i) kf[i] = kr[i];
+        // slot i: the K fragment ATT_Q64_KAHEAD slots ahead and the MFMA pair of fragment i; sched_barrier keeps a slot's work in it
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (i + ATT_Q64_KAHEAD < 8) kf[i + ATT_Q64_KAHEAD] = k_frag(BUF_B, i + ATT_Q64_KAHEAD);
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                s[b][i >> 2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[i], qf[b][i & 3], (i & 3) == 0 ? negm[b] : s[b][i >> 2], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        soft_piece(s[0][0], AttIC<0>{}, AttIC<8>{}, psum[0], pf[0][0]);
+        __builtin_amdgcn_sched_barrier(0);
+        soft_piece(s[0][0], AttIC<8>{}, AttIC<8>{}, psum[0], pf[0][0]);
+        __builtin_amdgcn_sched_barrier(0);
+        // Reference check, lane-local on the common path.  The rule is: a query row whose tile sum ptot = psum + psum' (its two
+        // lanes' half sums) is not < ATT_DEFER_SUM moves, and anything happens only if some row of the wave moves.  A half sum
+        // is a sum of exp2 values: non-negative or NaN.  If every lane has psum < ATT_DEFER_SUM / 2, no half sum is NaN and
+        // every ptot is the fp32 sum of two values below 8192: exact or rounded, it is below 16384 (rounding is monotonic and
+        // 16384 - ulp is representable), so no row moves and the rule does nothing: skipping it leaves the same bits.
+        // Otherwise (some psum >= 8192 or NaN) the rule itself runs, shuffle and all, unchanged.  So the pre-check only ever
+        // ADDS evaluations of the rule, never replaces its outcome.
+        f16x8 vf[8];
+        soft_piece(s[0][1], AttIC<0>{}, AttIC<8>{}, psum[0], pf[0][1]);
+        __builtin_amdgcn_sched_barrier(0);
+        soft_piece(s[0][1], AttIC<8>{}, AttIC<8>{}, psum[0], pf[0][1]);
+        if (__any(!(psum[0] < 0.5f * ATT_DEFER_SUM))) reference_rule(0, s, psum[0], pf, false);
+        l_run[0] += psum[0];
+        vf[0] = v_frag(BUF_B, 0);
+        vf[1] = v_frag(BUF_B, 1);
+        soft_piece(s[1][0], AttIC<0>{}, AttIC<8>{}, psum[1], pf[1][0]);
+        __builtin_amdgcn_sched_barrier(0);
+        soft_piece(s[1][0], AttIC<8>{}, AttIC<8>{}, psum[1], pf[1][0]);
+        __builtin_amdgcn_sched_barrier(0);
+        soft_piece(s[1][1], AttIC<0>{}, AttIC<8>{}, psum[1], pf[1][1]);
+        __builtin_amdgcn_sched_barrier(0);
+        soft_piece(s[1][1], AttIC<8>{}, AttIC<8>{}, psum[1], pf[1][1]);
+        if (__any(!(psum[1] < 0.5f * ATT_DEFER_SUM))) reference_rule(1, s, psum[1], pf, false);
+        l_run[1] += psum[1];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (j + 2 < 8) vf[j + 2] = v_frag(BUF_B, j + 2);
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                o[b][j >> 2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[j], pf[b][(j >> 1) & 1][j & 1], o[b][j >> 2], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (t + 1 < ntiles) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        k_head(BUF_B ^ TILE_B);                           // (the last tile's are not used: reads inside the LDS image)
+    };
+
+    dma_tile(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    edge_tile(0, 0);
+    const bool ragged = (S & (ATT_TILE - 1)) != 0;
+    const int loop_end = ragged ? ntiles - 1 : ntiles;   // loop tiles: [1, loop_end)
+    if (1 < loop_end) {
+        k_head(TILE_B);
+        for (int t = 1;;) {
+            loop_tile(AttIC<1>{}, t);
+            if (++t >= loop_end) break;
+            loop_tile(AttIC<0>{}, t);
+            if (++t >= loop_end) break;
+        }
+    }
+    if (ragged && ntiles > 1) edge_tile(ntiles - 1, ((ntiles - 1) & 1) * TILE_B);
+
+    // O leaves through the K / V buffers (free after the last barrier) as whole 128-byte rows per (token, head): the wave's 64
+    // rows x 128 B in its own 8 KB, 16-byte chunk c of row r in slot c ^ (r & 7); then 8 lanes store one row, 16 bytes each
+    if (__builtin_amdgcn_readfirstlane((((size_t)out | (size_t)(ldo * 2)) & 15) == 0)) {
+        char* ob = smem_att + wave * (64 * D * 2);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const float l_tot = l_run[b] + __shfl_xor(l_run[b], 32, 64);
+            const float inv = 1.0f / l_tot;
+            const int row = b * 32 + l31;
+#pragma unroll
+            for (int db = 0; db < DB; ++db)
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) {
+                    f16x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = (f16)(o[b][db][4 * qd + e] * inv);
+                    *(f16x4*)(ob + row * (D * 2) + (((db * 4 + qd) ^ (row & 7)) * 16) + lh * 8) = v;
+                }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int row = i * 8 + (lane >> 3), ch = lane & 7, qi = q0 + row;
+            const f16x8 v = *(const f16x8*)(ob + row * (D * 2) + ((ch ^ (row & 7)) * 16));
+            if (qi < S) *(f16x8*)(out + ((size_t)frame * S + qi) * ldo + head * D + ch * 8) = v;
+        }
+        return;
+    }
+    // (an output whose rows are not 16-byte aligned: per-lane 8-byte stores, as attn_spatial_kernel)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const float l_tot = l_run[b] + __shfl_xor(l_run[b], 32, 64);
+        const float inv = 1.0f / l_tot;
+        const int qi = q0 + b * 32 + l31;
+        if (qi < S) {
+            f16* op = out + ((size_t)frame * S + qi) * ldo + head * D;
+#pragma unroll
+            for (int db = 0; db < DB; ++db)
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) {
+                    f16x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = (f16)(o[b][db][4 * qd + e] * inv);
+                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = v;
+                }
+        }
+    }
+}
+
 template <int D, int QB>
 static int launch_attn_spatial(const void* q, const void* k, const void* v, void* out, int nframes, int heads, int S,
                                int ldq, int ldk, int ldv, int ldo, float c, hipStream_t st) {
@@ -361,10 +709,15 @@ static int launch_attn_spatial(const void* q, const void* k, const void* v, void
     const int nqb = cdiv(S, 128 * QB);
     const long long total = (long long)nqb * heads * nframes;
     if (total > 0x7ffffff0LL) return MOFA_EINVAL;
+    // (64 queries per wave at D = 64: the hand-scheduled kernel, same grid, LDS and arguments)
+    const auto kern = [] {
+        if constexpr (D == 64 && QB == 2) return &attn_spatial_q64_kernel;
+        else return &attn_spatial_kernel<D, QB>;
+    }();
     static LaunchSetup setup;
-    if (setup.cus([](int) { return mofa_lds_optin((const void*)attn_spatial_kernel<D, QB>, LDS); }) == 0) return MOFA_ELAUNCH;
+    if (setup.cus([kern](int) { return mofa_lds_optin((const void*)kern, LDS); }) == 0) return MOFA_ELAUNCH;
     dim3 grid((unsigned)(8 * ((total + 7) / 8)));              // (the kernel's XCD-aware work order)
-    hipLaunchKernelGGL((attn_spatial_kernel<D, QB>), grid, dim3(256), LDS, st, (const f16*)q, (const f16*)k, (const f16*)v,
+    hipLaunchKernelGGL(kern, grid, dim3(256), LDS, st, (const f16*)q, (const f16*)k, (const f16*)v,
                        (f16*)out, heads, S, ldq, ldk, ldv, ldo, c, nqb, (int)total);
     MOFA_CHECK_LAUNCH();
     return MOFA_OK;
