@@ -261,6 +261,24 @@ int mofa_attn_temporal_long_window_f16(const void* q, const void* k, const void*
 int mofa_attn_temporal_stream_local_f16(const void* q, const void* k, const void* v, void* out,
                                         int nclips, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
                                         float scale, int radius, int anchor, mofa_stream_t stream);
+/* Streaming temporal self-attention over 1 <= T <= 1024 frames under ANY window of the rule above, dense included: the row
+ * layout, the strides, head_dim in {64, 128} and the scale convention of mofa_attn_temporal_stream_local_f16,
+ *     query frame i sees key frame j  iff  j < anchor  or  |i - j| <= radius
+ * under radius >= 0 (no upper limit: radius >= T - 1 hides nothing and is clamped; that is dense attention) and
+ * 0 <= anchor <= T.  One wave owns a sequence and one 32-frame tile slot of K and V in LDS.  Per 32-query block it walks, in
+ * ascending order and each once, the key tiles that hold a key visible to some query of the block -- tiles 0 .. ceil(anchor /
+ * 32) - 1 and the tiles of frames q0 - radius .. q0 + 31 + radius, clipped to the clip -- and does not read the others; across
+ * the tiles it keeps a running maximum, a running sum and fp32 accumulators, rescaled when the maximum moves (exp2 form, P
+ * rounded to fp16 before P V, one multiplication by 1 / sum at the end).  A hidden key of a visited tile contributes an exact 0
+ * whatever the running maximum is.  K and V of a sequence are read once per query block that sees them; rows of frames >= T are
+ * never read or written.  Precondition: K and V of all T frames are finite -- an invisible frame of a visited tile is multiplied
+ * by its zero probability.  Calls whose rules hide nothing (radius >= T - 1, or anchor == T) give equal bits; the output is NOT
+ * bitwise that of the one-pass kernels (mofa_attn_temporal_long*_f16, ..._stream_local_f16) where both apply: the sum is taken
+ * in another order.  MOFA_EINVAL for everything mofa_attn_temporal_long_f16 refuses, with T > 1024 in place of T > 128, and for
+ * radius < 0, anchor < 0 or anchor > T -- all checked before any device call. */
+int mofa_attn_temporal_stream_f16(const void* q, const void* k, const void* v, void* out,
+                                  int nclips, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
+                                  float scale, int radius, int anchor, mofa_stream_t stream);
 /* in-place row softmax of an fp16 [rows][cols] matrix (VAE mid-block attention, 1 head x 512) */
 int mofa_softmax_rows_f16(void* x, int rows, int cols, int ld, mofa_stream_t stream);
 

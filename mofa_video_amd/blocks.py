@@ -24,8 +24,10 @@ from .weights import (f32, fold_up2, interleave_geglu, pack_conv3d_t3, pack_conv
 
 BIG = 1 << 30
 # local temporal attention (Ctx.local): clips of up to this many frames go to ops.attn_temporal_local, whose kernel stages the
-# whole clip's keys; longer ones to ops.attn_temporal_local_stream (four key tiles in a ring, radius and anchor <= 32)
+# whole clip's keys; longer ones to ops.attn_temporal_local_stream (four key tiles in a ring, radius and anchor <= 32) or, under a
+# window beyond the ring's limits, to ops.attn_temporal_stream (an online-softmax walk over the visible key tiles)
 LOCAL_STREAM_ABOVE = 128
+RING_RADIUS = RING_ANCHOR = 32
 
 
 class Sub:
@@ -500,7 +502,12 @@ class TransformerSpatioTemporal:
             if c.local is None:
                 a = ops.attn_temporal(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim)
             else:
-                local = ops.attn_temporal_local if T <= LOCAL_STREAM_ABOVE else ops.attn_temporal_local_stream
+                if T <= LOCAL_STREAM_ABOVE:
+                    local = ops.attn_temporal_local
+                elif c.local[0] <= RING_RADIUS and c.local[1] <= RING_ANCHOR:
+                    local = ops.attn_temporal_local_stream
+                else:
+                    local = ops.attn_temporal_stream
                 a = local(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim, local=c.local)
         elif c.local is not None:
             # local temporal attention on a frame shard (par.window_keys): this rank's queries see their band and the anchor

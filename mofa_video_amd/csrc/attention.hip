@@ -19,6 +19,8 @@
 //   mofa_attn_temporal_long_local_f16: its form under a per-query rule (a band round the query plus the first frames).
 //   mofa_attn_temporal_long_window_f16: that rule for a frame shard (Tq query frames, key slots = anchor frames + band frames).
 //   One body (attn_temporal_long_body.inc) included by the four kernels, one launcher, one dispatch, one argument check.
+//   mofa_attn_temporal_stream_local_f16: the per-query rule for 1 <= T <= 1024 under radius <= 32 and anchor <= 32 (four key tiles);
+//   mofa_attn_temporal_stream_f16: any radius and anchor, dense included, 1 <= T <= 1024: an online-softmax walk over the key tiles.
 //
 // mofa_transpose_v_f16, mofa_softmax_rows_f16: the two helpers of the VAE mid-block attention (scores materialised by implicit GEMMs).
 
@@ -1270,6 +1272,183 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_local_kernel(co
         for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
     }
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Streaming temporal attention under ANY window of the local rule, dense included: 1 <= T <= 1024 frames, radius >= 0 (the host
+// clamps it to T - 1), 0 <= anchor <= T.  One wave owns one sequence and ONE 32-row tile slot of K and V in LDS (the KT = 1
+// geometry: four waves a workgroup at D = 64, two at D = 128).  Per 32-query block q0 it walks, in ascending frame order and each
+// once, the key tiles that hold a key some query of the block can see
+//   anchor tiles  0 .. ceil(anchor / 32) - 1
+//   band tiles    (max(q0 - radius, 0) >> 5) .. (min(q0 + 31 + radius, T - 1) >> 5), those not among the anchor tiles
+// and never reads the others.  Across the tiles it keeps, per query, a running maximum m, this lane half's part l of the running
+// sum (the halves meet once, after the last tile) and the fp32 O^T accumulators; per tile
+//   m' = max(m, tile maximum over the VISIBLE keys)     a = exp2((m - m') c2)     l = a l + sum p     O^T = a O^T + V^T P^T
+// with p = exp2((s - m') c2) rounded to fp16 for P V, as in the long kernel, and one multiplication by 1 / l at the end.  a is set
+// to 1 where m' = m, and O^T is rescaled only where some lane's maximum moved (the skip changes no bit).
+// A hidden key's probability is SET to 0, not left to exp2: a visited tile can hide every key of a row whose maximum is still the
+// initial -1e30 (anchor = 0: the block's first band tile lies wholly below the band of its last queries whenever radius % 32 != 0),
+// and there exp2((s - m') c2) is exp2(+huge) = infinity (exp2(0) = 1 had the score been replaced by -1e30 first), which the
+// rescale by a = 0 at the row's first visible key turns into NaN.  With the select such a tile leaves m, l and O^T as they were.  Every row meets a
+// visible key in some visited tile (itself), so l > 0 at the end.
+// The walk is the same for a rule that hides nothing however it is spelt (radius >= T - 1, or anchor = T): all tiles, ascending,
+// every probability from exp2 -- equal bits.
+// The tile after the current one -- the next block's first tile after a block's last -- travels to registers under the current
+// tile's arithmetic and enters the slot behind the tile's last LDS read (s_waitcnt + wave barrier on both sides, as in the ring
+// kernel).  Frame rows >= T are not read (they are the next clip's) and are written as zero; K and V of all T frames must be
+// finite: a hidden frame of a visited tile is read and multiplied by its zero.  Query rows >= T take the rule of row T - 1 and
+// are neither loaded nor stored.  K and V of a sequence are read once per query block that sees them (from L2 after the first).
+// ---------------------------------------------------------------------------------------------------
+template <int D, int WPB>
+__global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                        const f16* __restrict__ v, f16* __restrict__ out,
+                                                                        long long nseq, int T, int HW, int heads, int ld,
+                                                                        int ldkv, int ldo, float scale, int radius, int anchor) {
+    constexpr int KK = D / 16, DB = D / 32, KSTR = D + 8, VSTR = D + 32;
+    extern __shared__ __attribute__((aligned(16))) char smem_tsd[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long seq = (long long)blockIdx.x * WPB + wave;
+    if (seq >= nseq) return;                                       // (no workgroup barrier below: LDS regions are per wave)
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int head = (int)(seq % heads);
+    const long long bp = seq / heads;
+    const int p = (int)(bp % HW);
+    const int b = (int)(bp / HW);
+    const size_t base = ((size_t)b * T * HW + p);                  // q / k / v / out token row of frame 0
+    f16* wK = (f16*)smem_tsd + (size_t)wave * (32 * (KSTR + VSTR));
+    f16* wV = wK + 32 * KSTR;
+    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int nA = (anchor + 31) >> 5;                             // anchor tiles
+    const auto first_tile = [&](int q0) { return nA > 0 ? 0 : max(q0 - radius, 0) >> 5; };
+
+    f16x8 qf[KK];
+    {
+        const f16* qp = q + (base + (size_t)(l31 < T ? l31 : 0) * HW) * ld + head * D + lh * 8;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) qf[kk] = l31 < T ? *(const f16x8*)(qp + kk * 16) : zero8;
+    }
+    {
+        TemporalStreamTile<D> t0;
+        t0.load(k, v, base, HW, ldkv, head, T, first_tile(0) * 32, lane);
+        t0.store(wK, wV, lane);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this wave's LDS writes are in place
+    __builtin_amdgcn_wave_barrier();
+
+    const float c2 = scale * 1.4426950408889634f;
+    const int tr_off = (((lane & 15) >> 2) + 4 * lh) * VSTR + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+#pragma unroll 1
+    for (int q0 = 0; q0 < T; q0 += 32) {
+        // the next block's Q fragments are fetched under this block's arithmetic
+        f16x8 qn[KK];
+        {
+            const int qi = q0 + 32 + l31;
+            const f16* qp = q + (base + (size_t)(qi < T ? qi : 0) * HW) * ld + head * D + lh * 8;
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) qn[kk] = qi < T ? *(const f16x8*)(qp + kk * 16) : zero8;
+        }
+        // the block's walk (wave-uniform): tiles 0 .. nA - 1, then band0 .. last
+        const int band0 = max(max(q0 - radius, 0) >> 5, nA);
+        const int last = max(min(q0 + 31 + radius, T - 1) >> 5, nA - 1);
+        // this lane's query and its band [lo, hi1)
+        const int qi = min(q0 + l31, T - 1);
+        const int lo = max(qi - radius, 0), hi1 = min(qi + radius, T - 1) + 1;
+
+        float m = -1e30f, mc = m * c2, l = 0.f;
+        f32x16 o[DB];
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+
+        int kt = nA > 0 ? 0 : band0;
+#pragma unroll 1
+        for (;;) {
+            int nk = kt + 1;
+            if (nk >= nA && nk < band0) nk = band0;
+            const bool more = nk <= last;
+            // the next tile of the walk travels to registers under this tile's arithmetic (after the last: nothing is read)
+            TemporalStreamTile<D> nt;
+            nt.load(k, v, base, HW, ldkv, head, T, more ? nk * 32 : q0 + 32 < T ? first_tile(q0 + 32) * 32 : T, lane);
+
+            const auto below = [](int n) { return (unsigned)((1ull << min(max(n, 0), 32)) - 1ull); };
+            const unsigned ml = (below(anchor - 32 * kt) | (below(hi1 - 32 * kt) & ~below(lo - 32 * kt))) >> (4 * lh);
+            // ---- S^T tile: s[r] = score(key = 32 kt + (r & 3) + 8 (r >> 2) + 4 lh, query = q0 + l31) ----
+            f32x16 s;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = 0.f;
+            {
+                const f16* kp = wK + l31 * KSTR + lh * 8;
+#pragma unroll
+                for (int kk = 0; kk < KK; ++kk) {
+                    const f16x8 kf = *(const f16x8*)(kp + kk * 16);
+                    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], s, 0, 0, 0);
+                }
+            }
+            float mx = m;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (ml & (1u << TL_SLOT(r))) mx = fmaxf(mx, s[r]);
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float mcn = mx * c2;
+            // a is SET to 1 where the maximum stayed: mc - mx c2 may be contracted into one fma, which returns the product's
+            // rounding error instead of 0 -- about 1e21 in size at m = -1e30, exp2 of which is 0 or infinity
+            const bool moved = mx != m;
+            const float a = moved ? __builtin_amdgcn_exp2f(mc - mcn) : 1.0f;   // m = -1e30 < mx: exp2(-huge) = 0
+            m = mx; mc = mcn;
+            float sum = 0.f;
+            f16x8 pf[2];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float e = __builtin_amdgcn_exp2f(fmaf(s[r], c2, -mc));
+                const float pr = (ml & (1u << TL_SLOT(r))) ? e : 0.f;      // hidden: exactly 0 whatever m is
+                sum += pr;
+                pf[r >> 3][r & 7] = (f16)pr;
+            }
+            l = fmaf(l, a, sum);
+            if (__any(moved)) {
+#pragma unroll
+                for (int db = 0; db < DB; ++db)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[db][r] *= a;
+            }
+            // ---- O^T[d][q] += V^T[d][key] P^T[key][q], k-slots as in the body file ----
+#pragma unroll
+            for (int db = 0; db < DB; ++db) {
+                const f16* vp = wV + tr_off + db * 32;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const f16x4 vl = lds_read_tr4(vp + (u * 16) * VSTR), vh = lds_read_tr4(vp + (u * 16 + 8) * VSTR);
+                    const f16x8 vf = {vl[0], vl[1], vl[2], vl[3], vh[0], vh[1], vh[2], vh[3]};
+                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[u], o[db], 0, 0, 0);
+                }
+            }
+            // ---- the next tile into the slot, after this tile's last LDS read ----
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            nt.store(wK, wV, lane);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            if (!more) break;
+            kt = nk;
+        }
+        l += __shfl_xor(l, 32, 64);
+        const float inv = 1.0f / l;
+        if (q0 + l31 < T) {
+            f16* op = out + (base + (size_t)(q0 + l31) * HW) * ldo + head * D;
+#pragma unroll
+            for (int db = 0; db < DB; ++db)
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) {
+                    f16x4 w;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) w[e] = (f16)(o[db][4 * qd + e] * inv);
+                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;
+                }
+        }
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
+    }
+}
 #undef TL_SLOT
 
 // waves per workgroup: as many as keep a workgroup's LDS at or below 42 KB (D = 64) / 37 KB (D = 128), at least one
@@ -1398,6 +1577,25 @@ extern "C" int mofa_attn_temporal_stream_local_f16(const void* q, const void* k,
             radius, anchor);
     };
     return head_dim == 64 ? launch(TemporalLongGeom<64, 4>{}) : launch(TemporalLongGeom<128, 4>{});
+}
+
+// the local rule for 1 <= T <= 1024 frames under ANY radius >= 0 and 0 <= anchor <= T, dense (radius >= T - 1) included
+// (attn_temporal_stream_kernel: an online-softmax walk over the visible key tiles).  radius >= T - 1 hides nothing and is clamped
+// (the kernel adds it to a frame index).  The KT = 1 geometry: one tile slot a wave, four (D = 64) / two (D = 128) waves a workgroup
+extern "C" int mofa_attn_temporal_stream_f16(const void* q, const void* k, const void* v, void* out, int nclips, int T, int HW,
+                                             int heads, int head_dim, int ld, int ldkv, int ldo, float scale, int radius,
+                                             int anchor, mofa_stream_t stream) {
+    if (!temporal_long_args_ok(q, k, v, out, nclips, T, HW, heads, head_dim, ld, ldkv, ldo, 1024)) return MOFA_EINVAL;
+    if (radius < 0 || anchor < 0 || anchor > T) return MOFA_EINVAL;
+    if (radius > T - 1) radius = T - 1;
+    const long long nseq = (long long)nclips * HW * heads;
+    const auto launch = [&](auto g) {
+        using G = decltype(g);
+        return launch_temporal_long<G, attn_temporal_stream_kernel<G::D, G::WPB>>(
+            nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale,
+            radius, anchor);
+    };
+    return head_dim == 64 ? launch(TemporalLongGeom<64, 1>{}) : launch(TemporalLongGeom<128, 1>{});
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -472,11 +472,13 @@ def attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=No
     """k/v hold T frames per clip; q holds Tq <= T (Tq < T: frame-sharded clip with all-gathered K/V).  key_mask: bit j =
     key frame j exists (padding frames of uneven shards in the gathered buffer are masked, never read).
     T > 32 (up to 128): plain self-attention only (Tq == T, no mask) through mofa_attn_temporal_long_f16; the sharded form
-    of such clips is ``attn_temporal_sharded``."""
+    of such clips is ``attn_temporal_sharded``.  T > 128 (up to 1024), self-attention: ``attn_temporal_stream``, dense."""
     Tq = T if Tq is None else Tq
     if T > 32 and (key_mask is not None or Tq != T):
         raise ValueError(f"temporal attention over {T} key frames with a key mask or Tq < T: frame-sharded clips are limited "
                          "to 32 key slots")
+    if T > 128:
+        return attn_temporal_stream(q, k, v, nclips, T, HW, heads, head_dim=head_dim, scale=scale, out=out)
     lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * Tq * HW, heads, head_dim, scale, out)
     if T > 32:
         t0 = TIMER.start() if TIMER is not None else None
@@ -599,6 +601,33 @@ def attn_temporal_local_stream(q, k, v, nclips, T, HW, heads, head_dim=64, scale
     if t0 is not None:
         Cc = heads * head_dim
         TIMER.stop("attn_temporal_stream_kernel", t0, flops=4.0 * T * min(T, 128) * Cc * nclips * HW, nbytes=8.0 * nclips * T * HW * Cc)
+    return out
+
+
+def stream_visible_pairs(T, radius, anchor):
+    """how many (query frame, key frame) pairs the local rule makes visible in a clip of T frames"""
+    return sum(len(set(range(min(anchor, T))) | set(range(max(i - radius, 0), min(i + radius, T - 1) + 1))) for i in range(T))
+
+
+def attn_temporal_stream(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=None, Tq=None, key_mask=None, local=None):
+    """temporal self-attention over clips of up to 1024 frames under ANY window of the local rule, through
+    mofa_attn_temporal_stream_f16 (an online-softmax walk over the key tiles the rule makes visible): local = (radius, anchor)
+    with radius >= 0 and 0 <= anchor <= T, or None = dense (every query sees every key).  The parameters of
+    ``attn_temporal_local`` in the same order, with the same refusals of ``Tq`` / ``key_mask``.  K and V of all T frames must be
+    finite.  Not bitwise the one-pass kernels' output where both apply (another summation order)."""
+    if key_mask is not None or Tq is not None:
+        raise ValueError("local temporal attention takes no key_mask and no Tq: the gathered-key path of frame-sharded clips has "
+                         "no per-query mask")
+    radius, anchor = (max(T - 1, 0), 0) if local is None else (int(x) for x in local)
+    lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * T * HW, heads, head_dim, scale, out)
+    t0 = TIMER.start() if TIMER is not None else None
+    L.check(lib.mofa_attn_temporal_stream_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, T, HW, heads, head_dim,
+                                              _ld(q), _ld(k), _ld(out), scale, radius, anchor, L.stream_ptr()),
+            "mofa_attn_temporal_stream_f16")
+    if t0 is not None:
+        Cc = heads * head_dim
+        TIMER.stop("attn_temporal_stream_kernel", t0, flops=4.0 * stream_visible_pairs(T, radius, anchor) * Cc * nclips * HW,
+                   nbytes=8.0 * nclips * T * HW * Cc)
     return out
 
 

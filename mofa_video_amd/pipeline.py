@@ -67,6 +67,8 @@ MAX_TEMPORAL_FRAMES_LONG = 128  # mofa_attn_temporal_long_f16 (four key tiles): 
 # launches of a denoise step were read for (the row and offset arithmetic at 2 x 256 x 9216 rows)
 MAX_TEMPORAL_FRAMES_STREAM = 256
 STREAM_RADIUS = STREAM_ANCHOR = 32
+# temporal_stream=True lifts the window rule: above 128 frames a window beyond the ring's limits, and no window at all (dense, the
+# reference's own arithmetic), run through mofa_attn_temporal_stream_f16 -- up to the same MAX_TEMPORAL_FRAMES_STREAM
 
 
 def _temporal_window(value):
@@ -169,13 +171,17 @@ class _Step:
 class FlowControlNetPipeline:
     def __init__(self, vae=None, image_encoder=None, unet=None, controlnet=None, scheduler=None,
                  feature_extractor=None, parallel=None, round_latents_to_fp16=False, max_temporal_frames: int = MAX_TEMPORAL_FRAMES,
-                 temporal_window=None):
+                 temporal_window=None, temporal_stream: bool = False):
         """parallel: optional ``parallel.FrameParallel`` -- this process then computes one CFG half / one frame shard
         of every clip (mofa_video_amd/parallel.py); all ranks must call the pipeline with identical inputs.
         round_latents_to_fp16: round the latents to fp16 after every Euler step, as the reference's fp16 run does.
         max_temporal_frames: the most frames one forward pass may hold (``num_frames``, or ``window_size`` of the window
         loop), 1 .. 128, or up to 256 under a ``temporal_window`` of radius <= 32 and anchor <= 32 (the temporal attention of
         more than 128 frames is mofa_attn_temporal_stream_local_f16; nothing at full geometry has been run above 128 frames).
+        temporal_stream: True lifts that rule: up to 256 under ANY valid ``temporal_window``, None (dense) included.  Above 128
+        frames dense attention and windows of radius > 32 or anchor > 32 then run through mofa_attn_temporal_stream_f16 (an
+        online-softmax walk over the visible key tiles); everything else launches what it launches without the keyword.
+        Nothing at full geometry has been run above 128 frames, and the memory of such a pass was not examined.
         Above the default of 32 the temporal attention runs through mofa_attn_temporal_long_f16; clips
         sharded over ranks (``parallel``) stay limited to 32 unless the parallel object was built with ``max_key_slots=`` (up
         to 128): then to the smaller of the two.
@@ -191,13 +197,20 @@ class FlowControlNetPipeline:
         checked over gloo on the CPU and on virtual ranks on one GPU; nothing was run on more than one GPU.  Nothing is
         claimed about what the released checkpoints produce under a window."""
         self.temporal_window = _temporal_window(temporal_window)
-        streams = self.temporal_window is not None and self.temporal_window[0] <= STREAM_RADIUS \
-            and self.temporal_window[1] <= STREAM_ANCHOR
+        if not isinstance(temporal_stream, bool):
+            raise ValueError(f"temporal_stream must be True or False, got {temporal_stream!r}")
+        self.temporal_stream = temporal_stream
+        streams = temporal_stream or (self.temporal_window is not None and self.temporal_window[0] <= STREAM_RADIUS
+                                      and self.temporal_window[1] <= STREAM_ANCHOR)
         if isinstance(max_temporal_frames, bool) or not isinstance(max_temporal_frames, int) \
                 or not 1 <= max_temporal_frames <= (MAX_TEMPORAL_FRAMES_STREAM if streams else MAX_TEMPORAL_FRAMES_LONG):
+            if temporal_stream:
+                raise ValueError(f"max_temporal_frames must be an integer in 1 .. {MAX_TEMPORAL_FRAMES_STREAM} with "
+                                 f"temporal_stream=True, got {max_temporal_frames!r}")
             raise ValueError(f"max_temporal_frames must be an integer in 1 .. {MAX_TEMPORAL_FRAMES_LONG}, or up to "
                              f"{MAX_TEMPORAL_FRAMES_STREAM} with temporal_window=(radius <= {STREAM_RADIUS}, anchor <= "
-                             f"{STREAM_ANCHOR}), got {max_temporal_frames!r} with temporal_window={temporal_window!r}")
+                             f"{STREAM_ANCHOR}), got {max_temporal_frames!r} with temporal_window={temporal_window!r}"
+                             f" (temporal_stream=True: up to {MAX_TEMPORAL_FRAMES_STREAM} under any window, none included)")
         self.max_temporal_frames = max_temporal_frames
         self.vae, self.image_encoder, self.unet, self.controlnet = vae, image_encoder, unet, controlnet
         self.scheduler, self.feature_extractor = scheduler, feature_extractor
@@ -237,7 +250,7 @@ class FlowControlNetPipeline:
         except OSError:
             sch = EulerDiscreteScheduler()
         names = ("face_controlnet", "drag_controlnet", "parallel", "round_latents_to_fp16", "feature_extractor", "max_temporal_frames",
-                 "temporal_window")
+                 "temporal_window", "temporal_stream")
         kw = {k: v for k, v in modules.items() if k in names}
         if controlnet is not None:
             kw["controlnet"] = controlnet
@@ -610,10 +623,10 @@ def _blend_residuals(df, mf, dd, md, masks, nframes):
 class HybridFlowControlNetPipeline(FlowControlNetPipeline):
     def __init__(self, vae=None, image_encoder=None, unet=None, face_controlnet=None, drag_controlnet=None,
                  scheduler=None, feature_extractor=None, parallel=None, round_latents_to_fp16=False,
-                 max_temporal_frames: int = MAX_TEMPORAL_FRAMES, temporal_window=None):
+                 max_temporal_frames: int = MAX_TEMPORAL_FRAMES, temporal_window=None, temporal_stream: bool = False):
         super().__init__(vae, image_encoder, unet, face_controlnet, scheduler, feature_extractor, parallel=parallel,
                          round_latents_to_fp16=round_latents_to_fp16, max_temporal_frames=max_temporal_frames,
-                         temporal_window=temporal_window)
+                         temporal_window=temporal_window, temporal_stream=temporal_stream)
         self.face_controlnet, self.drag_controlnet = face_controlnet, drag_controlnet
 
     @torch.no_grad()
@@ -843,10 +856,10 @@ class KeypointFlowControlNetPipeline(FlowControlNetPipeline):
 
     def __init__(self, vae=None, image_encoder=None, unet=None, controlnet=None, scheduler=None, feature_extractor=None,
                  parallel=None, round_latents_to_fp16=False, drag_controlnet=None, overlap_decode=True,
-                 max_temporal_frames: int = MAX_TEMPORAL_FRAMES, temporal_window=None):
+                 max_temporal_frames: int = MAX_TEMPORAL_FRAMES, temporal_window=None, temporal_stream: bool = False):
         super().__init__(vae, image_encoder, unet, controlnet, scheduler, feature_extractor, parallel=parallel,
                          round_latents_to_fp16=round_latents_to_fp16, max_temporal_frames=max_temporal_frames,
-                         temporal_window=temporal_window)
+                         temporal_window=temporal_window, temporal_stream=temporal_stream)
         self.drag_controlnet = drag_controlnet
         self.overlap_decode = overlap_decode
 
