@@ -279,6 +279,32 @@ int mofa_attn_temporal_stream_local_f16(const void* q, const void* k, const void
 int mofa_attn_temporal_stream_f16(const void* q, const void* k, const void* v, void* out,
                                   int nclips, int T, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
                                   float scale, int radius, int anchor, mofa_stream_t stream);
+/* The streaming walk of mofa_attn_temporal_stream_f16 on the key buffer of a FRAME SHARD: Tq >= 1 query frames (rows of q / out,
+ * clip stride Tq*HW) against 1 <= S <= 1024 key SLOTS (rows of k / v, clip stride S*HW), head_dim 64 or 128.  `radius` selects
+ * one of two modes.
+ * Window mode, radius >= 0: the contract of mofa_attn_temporal_long_window_f16 with 1024 slots for 128 -- slots [0, anchor) are
+ * the global frames 0 .. anchor - 1, slot s >= anchor is the global frame band_frame0 + (s - anchor); the query of global frame
+ * g = q_frame0 + row sees the anchor slots and every band slot whose frame is >= anchor and within radius of g (a band slot that
+ * repeats an anchor frame counts zero times).  key_mask must be NULL.  Refused: anchor < 0 or > S, band_frame0 < 0 or above
+ * 2^30, q_frame0 < band_frame0 or q_frame0 + Tq > band_frame0 + (S - anchor) (the queries' frames lie in the band); radius above
+ * S - 1 is clamped (it hides nothing), so that no frame sum overflows.  Per 32-query block the walk visits, ascending and once
+ * each, the anchor tiles and then the band tiles that hold a slot some query of the block can see, and no other tile.
+ * Precondition: K and V of all S slots are finite -- a hidden slot of a visited tile is multiplied by its exact 0.
+ * Dense mode, radius == -1: anchor, q_frame0 and band_frame0 must be 0.  key_mask is HOST memory of ceil(S / 32) words read
+ * during the call, bit j % 32 of word j / 32 = slot j exists; NULL = every slot; bits at or above S are ignored; a mask with no
+ * live slot is refused.  Every query sees every live slot; the walk visits the tiles whose mask word is non-zero; the K / V rows
+ * of a dead slot are never read from memory (the padding slots of a gathered buffer may hold anything, NaN included) and have
+ * weight exactly 0.  Tq above 2^30 is refused.
+ * In both modes the mask words travel as kernel arguments (no device allocation, no copy), query rows >= Tq are neither read nor
+ * written, and slot rows >= S (the next clip's) are not read.  Equal bits: (a) dense, NULL mask, Tq == S: those of
+ * mofa_attn_temporal_stream_f16 dense; (b) dense, NULL mask, Tq < S on the q rows f0 .. f0 + Tq - 1 of a clip: those rows of (a);
+ * (c) window with anchor = 0, q_frame0 = band_frame0 = 0, Tq == S: mofa_attn_temporal_stream_f16 under (radius, 0); (d) the
+ * contents of dead slots change no bit.  MOFA_EINVAL for everything mofa_attn_temporal_long_f16 refuses (with S in place of T
+ * and 1024 in place of 128), for Tq < 1, radius < -1 and for every rule above -- all checked before any device call. */
+int mofa_attn_temporal_stream_shard_f16(const void* q, const void* k, const void* v, void* out,
+                                        int nclips, int Tq, int S, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
+                                        float scale, int radius, int anchor, int q_frame0, int band_frame0,
+                                        const uint32_t* key_mask, mofa_stream_t stream);
 /* in-place row softmax of an fp16 [rows][cols] matrix (VAE mid-block attention, 1 head x 512) */
 int mofa_softmax_rows_f16(void* x, int rows, int cols, int ld, mofa_stream_t stream);
 

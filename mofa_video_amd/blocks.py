@@ -28,6 +28,15 @@ BIG = 1 << 30
 # window beyond the ring's limits, to ops.attn_temporal_stream (an online-softmax walk over the visible key tiles)
 LOCAL_STREAM_ABOVE = 128
 RING_RADIUS = RING_ANCHOR = 32
+# frame-sharded clips: a rank's attention over more than this many key slots goes to ops.attn_temporal_stream_shard, on a parallel
+# object built with stream_keys=True (without the keyword such a slot count is refused before a block runs, or compacted)
+SHARD_STREAM_ABOVE = 128
+
+
+def _stream_keys(par, slots):
+    """whether a frame shard's temporal attention over ``slots`` key slots takes the streaming entry: up to 128 slots every
+    object launches what it launched before the keyword existed"""
+    return slots > SHARD_STREAM_ABOVE and bool(getattr(par, "stream_keys", False))
 
 
 class Sub:
@@ -523,8 +532,9 @@ class TransformerSpatioTemporal:
             q = self.tattn1.q(fn)
             work.wait()
             kv = ops.igemm(hid, self.tattn1.wqkv[Cc:])
-            a = ops.attn_temporal_window(q, kv[:, :Cc], kv[:, Cc:], 1, wplan.S, HW, self.heads, head_dim=self.tattn1.head_dim,
-                                         Tq=T, local=c.local, q_frame0=par.f0, band_frame0=wplan.b0)
+            window = ops.attn_temporal_stream_shard if _stream_keys(par, wplan.S) else ops.attn_temporal_window
+            a = window(q, kv[:, :Cc], kv[:, Cc:], 1, wplan.S, HW, self.heads, head_dim=self.tattn1.head_dim,
+                       Tq=T, local=c.local, q_frame0=par.f0, band_frame0=wplan.b0)
         else:
             # this rank holds T of the clip's T_full frames.  The K|V projection writes this shard's slot of the gather
             # buffer, one all_gather_into_tensor (asynchronous, RCCL's stream) fills the other slots while the Q
@@ -543,8 +553,9 @@ class TransformerSpatioTemporal:
                 q = self.tattn1.q(fn)
                 work.wait()
                 kv = ops.igemm(hid, self.tattn1.wqkv[Cc:])
-                a = ops.attn_temporal_sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
-                                              head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
+                sharded = ops.attn_temporal_stream_shard if _stream_keys(par, par.kv_slots) else ops.attn_temporal_sharded
+                a = sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
+                            head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
             elif par.kv_slots <= par.max_key_slots and par.kv_inplace:
                 fn = fn if fn is not None else self.tnorm1(f)
                 kv, own = par.kv_buffer(HW, 2 * Cc, fn.device)
@@ -552,8 +563,9 @@ class TransformerSpatioTemporal:
                 work = par.kv_gather_begin(kv, HW)
                 q = self.tattn1.q(fn)
                 work.wait()
-                a = ops.attn_temporal_sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
-                                              head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
+                sharded = ops.attn_temporal_stream_shard if _stream_keys(par, par.kv_slots) else ops.attn_temporal_sharded
+                a = sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
+                            head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
             else:   # more than par.max_key_slots slots after padding (31 frames over 3 shards; 128 over 3 at a limit of 128), or the in-place path failed
                     # its self-check on this transport (parallel.FrameParallel.self_check): compact to T_full frames
                 fn = fn if fn is not None else self.tnorm1(f)
@@ -562,8 +574,8 @@ class TransformerSpatioTemporal:
                 ops.copy2d(k, kv[:, :Cc])
                 ops.copy2d(v, kv[:, Cc:])
                 kv = par.gather_frames(kv, HW)
-                a = ops.attn_temporal_sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.T_full, HW, self.heads,
-                                              head_dim=self.tattn1.head_dim, Tq=T)
+                sharded = ops.attn_temporal_stream_shard if _stream_keys(par, par.T_full) else ops.attn_temporal_sharded
+                a = sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.T_full, HW, self.heads, head_dim=self.tattn1.head_dim, Tq=T)
         # temporal cross-attention row vector.  diffusers 0.24.0 quirk: token row (b, s) of the GLOBAL batch takes the
         # context of batch (b*HW + s) mod B_global; v_tm has one row per global batch element.
         Bg = v_tm.shape[0]

@@ -21,6 +21,8 @@
 //   One body (attn_temporal_long_body.inc) included by the four kernels, one launcher, one dispatch, one argument check.
 //   mofa_attn_temporal_stream_local_f16: the per-query rule for 1 <= T <= 1024 under radius <= 32 and anchor <= 32 (four key tiles);
 //   mofa_attn_temporal_stream_f16: any radius and anchor, dense included, 1 <= T <= 1024: an online-softmax walk over the key tiles.
+//   mofa_attn_temporal_stream_shard_f16: that walk for a frame shard, Tq query frames against 1 <= S <= 1024 key slots: the window
+//   rule on anchor + band slots, or dense under a key mask whose dead slots are never read.
 //
 // mofa_transpose_v_f16, mofa_softmax_rows_f16: the two helpers of the VAE mid-block attention (scores materialised by implicit GEMMs).
 
@@ -1449,6 +1451,239 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_kernel(const f1
         for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
     }
 }
+
+// ---------------------------------------------------------------------------------------------------
+// The streaming walk on the key buffer of a FRAME SHARD: Tq query rows of a clip (clip stride Tq * HW in q / out) against
+// 1 <= S <= 1024 key SLOTS (clip stride S * HW in k / v).  The tile walk, the online softmax and the KT = 1 geometry are those of
+// attn_temporal_stream_kernel above (its header comment holds here, the -1e30 hazard and its select included); what differs is
+// which slots a query sees.  ONE rule serves both forms of a sharded clip, a slot being seen iff the window shows it AND it exists:
+//   window   slots [0, anchor) hold the global frames 0 .. anchor - 1, slot s >= anchor the global frame band_frame0 + (s - anchor);
+//            the query of global frame g = q_frame0 + row sees the anchor slots and the band slots [lo, hi1) of
+//            attn_temporal_long_window_kernel (frame >= anchor and within radius of g: a band slot that repeats an anchor frame
+//            counts zero times).  Every slot below S exists.  K and V of every slot must be finite.
+//   dense    the host passes radius = 2^30, anchor = 0 and both frames 0, so the window is [0, S) for every query, and the 32 mask
+//            words say which slots exist: bit j % 32 of word j / 32 (the host clears the bits at and above S).  The K / V rows of a
+//            slot that does not exist are never read from memory -- the padding slots of a gathered buffer hold whatever the
+//            allocator left -- and enter the tile as zeros.
+// The words travel as kernel arguments and live in ONE VGPR, lane j (and j + 32) holding word j: the word of the running tile is
+// read with v_readlane, so the array is never indexed in private memory, and the ballot of the non-zero words is the set of tiles
+// that exist.  Per 32-query block the walk visits, ascending and once each, the anchor tiles and the band tiles that hold a slot
+// some query of the block can see (the union of the queries' [lo, hi1) is [lo of the first, hi1 of the last)), each only if it
+// exists; no other tile is visited.  The tiles of a block are one wave-uniform 32-bit set.
+// Bit-level anchors, kept true by running the same arithmetic on the same visible keys in the same order:
+//   (a) dense, every slot, Tq == S: the bits of attn_temporal_stream_kernel dense;
+//   (b) dense, every slot, Tq < S, on the q rows f0 .. f0 + Tq - 1 of a clip: the bits of those rows of (a) -- in dense mode a
+//       query's arithmetic depends on its own row and the ascending walk over all tiles, not on how the 32-query blocks are
+//       aligned (the rescale skipped where no lane's maximum moved changes no bit);
+//   (c) window with anchor = 0, q_frame0 = band_frame0 = 0, Tq == S: the bits of attn_temporal_stream_kernel under (radius, 0);
+//   (d) the contents of slots that do not exist change no bit.
+// Query rows >= Tq take the rule of row Tq - 1 and are neither loaded nor stored; slot rows >= S are the next clip's and are not
+// read.
+// ---------------------------------------------------------------------------------------------------
+struct TemporalShardWords {
+    unsigned w[32];
+};
+
+template <int D, int WPB>
+__global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_shard_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                              const f16* __restrict__ v, f16* __restrict__ out,
+                                                                              long long nseq, int Tq, int S, int HW, int heads,
+                                                                              int ld, int ldkv, int ldo, float scale, int radius,
+                                                                              int anchor, int q_frame0, int band_frame0,
+                                                                              TemporalShardWords words) {
+    constexpr int KK = D / 16, DB = D / 32, KSTR = D + 8, VSTR = D + 32;
+    constexpr int DC = D / 8, RPI = 64 / DC, NR = 32 / RPI;        // a tile in flight, as in TemporalStreamTile
+    extern __shared__ __attribute__((aligned(16))) char smem_tss[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long seq = (long long)blockIdx.x * WPB + wave;
+    if (seq >= nseq) return;                                       // (no workgroup barrier below: LDS regions are per wave)
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int head = (int)(seq % heads);
+    const long long bp = seq / heads;
+    const int p = (int)(bp % HW);
+    const int b = (int)(bp / HW);
+    const size_t base = ((size_t)b * S * HW + p);                  // k / v token row of slot 0
+    const size_t qbase = ((size_t)b * Tq * HW + p);                // q / out token row of the first query frame
+    f16* wK = (f16*)smem_tss + (size_t)wave * (32 * (KSTR + VSTR));
+    f16* wV = wK + 32 * KSTR;
+    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    const auto below = [](int n) { return (unsigned)((1ull << min(max(n, 0), 32)) - 1ull); };
+
+    // the 32 mask words in one register: lane j holds word j; exist = the tiles that hold a slot
+    unsigned mwv = 0;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) mwv = l31 == j ? words.w[j] : mwv;
+    const unsigned exist = (unsigned)__ballot(mwv != 0);
+    const auto word = [&](int kt) { return (unsigned)__builtin_amdgcn_readlane((int)mwv, kt); };
+
+    const int nA = (anchor + 31) >> 5;                             // anchor tiles
+    const int hi_f = band_frame0 + (S - anchor) - 1;               // the last band frame
+    // the tiles of the query block at q0 (wave-uniform): the anchor tiles and the band tiles of slots [lo of the block's first
+    // query, hi1 of its last), those that exist.  Never empty: a query's own frame is a slot (window); some slot exists (dense).
+    const auto tiles = [&](int q0) {
+        const int g0 = q_frame0 + q0, g1 = q_frame0 + min(q0 + 31, Tq - 1);
+        const int lo = anchor + max(max(g0 - radius, anchor), band_frame0) - band_frame0;
+        const int hi1 = anchor + min(g1 + radius, hi_f) - band_frame0 + 1;
+        unsigned t = below(nA);
+        if (lo < hi1) t |= below(((hi1 - 1) >> 5) + 1) & ~below(lo >> 5);
+        return t & exist;
+    };
+    // one 32-row tile of K and V in flight between memory and the slot: rows of slots that do not exist (and every row under a
+    // zero word) are not read and become zero
+    f16x8 gk[NR], gv[NR];
+    const int r0 = lane / DC, cc = lane % DC;
+    const auto tile_load = [&](int kt, unsigned w) {
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            const int i = u * RPI + r0;
+            gk[u] = zero8; gv[u] = zero8;
+            if ((w >> i) & 1u) {
+                const size_t off = (base + (size_t)(kt * 32 + i) * HW) * ldkv + head * D + cc * 8;
+                gk[u] = *(const f16x8*)(k + off);
+                gv[u] = *(const f16x8*)(v + off);
+            }
+        }
+    };
+    const auto tile_store = [&]() {
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            const int i = u * RPI + r0;
+            *(f16x8*)&wK[i * KSTR + cc * 8] = gk[u];
+            *(f16x8*)&wV[i * VSTR + cc * 8] = gv[u];
+        }
+    };
+
+    f16x8 qf[KK];
+    {
+        const f16* qp = q + (qbase + (size_t)(l31 < Tq ? l31 : 0) * HW) * ld + head * D + lh * 8;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) qf[kk] = l31 < Tq ? *(const f16x8*)(qp + kk * 16) : zero8;
+    }
+    unsigned tl = tiles(0);
+    {
+        const int kt0 = __builtin_ctz(tl);
+        tile_load(kt0, word(kt0));
+        tile_store();
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this wave's LDS writes are in place
+    __builtin_amdgcn_wave_barrier();
+
+    const float c2 = scale * 1.4426950408889634f;
+    const int tr_off = (((lane & 15) >> 2) + 4 * lh) * VSTR + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+#pragma unroll 1
+    for (int q0 = 0; q0 < Tq; q0 += 32) {
+        // the next block's Q fragments are fetched under this block's arithmetic
+        f16x8 qn[KK];
+        {
+            const int qi = q0 + 32 + l31;
+            const f16* qp = q + (qbase + (size_t)(qi < Tq ? qi : 0) * HW) * ld + head * D + lh * 8;
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) qn[kk] = qi < Tq ? *(const f16x8*)(qp + kk * 16) : zero8;
+        }
+        const unsigned tl_next = q0 + 32 < Tq ? tiles(q0 + 32) : 0u;
+        // this lane's query and its band slots [lo, hi1) (lo >= hi1: a query below the anchor whose band lies inside it)
+        const int g = q_frame0 + min(q0 + l31, Tq - 1);
+        const int lo = anchor + max(max(g - radius, anchor), band_frame0) - band_frame0;
+        const int hi1 = anchor + min(g + radius, hi_f) - band_frame0 + 1;
+
+        float m = -1e30f, mc = m * c2, l = 0.f;
+        f32x16 o[DB];
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+
+        int kt = __builtin_ctz(tl);
+        unsigned rest = tl & (tl - 1u);
+#pragma unroll 1
+        for (;;) {
+            const bool more = rest != 0u;
+            // the next tile of the walk -- after a block's last, the next block's first -- travels to registers under this tile's
+            // arithmetic (after the last tile of all: a zero word, nothing is read)
+            const unsigned nxt = more ? rest : tl_next;
+            const int nk = nxt ? __builtin_ctz(nxt) : 0;
+            tile_load(nk, nxt ? word(nk) : 0u);
+
+            const unsigned ml =
+                ((below(anchor - 32 * kt) | (below(hi1 - 32 * kt) & ~below(lo - 32 * kt))) & word(kt)) >> (4 * lh);
+            // ---- S^T tile: s[r] = score(slot = 32 kt + (r & 3) + 8 (r >> 2) + 4 lh, query = q0 + l31) ----
+            f32x16 s;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = 0.f;
+            {
+                const f16* kp = wK + l31 * KSTR + lh * 8;
+#pragma unroll
+                for (int kk = 0; kk < KK; ++kk) {
+                    const f16x8 kf = *(const f16x8*)(kp + kk * 16);
+                    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], s, 0, 0, 0);
+                }
+            }
+            float mx = m;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (ml & (1u << TL_SLOT(r))) mx = fmaxf(mx, s[r]);
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float mcn = mx * c2;
+            // a is SET to 1 where the maximum stayed (see attn_temporal_stream_kernel)
+            const bool moved = mx != m;
+            const float a = moved ? __builtin_amdgcn_exp2f(mc - mcn) : 1.0f;   // m = -1e30 < mx: exp2(-huge) = 0
+            m = mx; mc = mcn;
+            float sum = 0.f;
+            f16x8 pf[2];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float e = __builtin_amdgcn_exp2f(fmaf(s[r], c2, -mc));
+                const float pr = (ml & (1u << TL_SLOT(r))) ? e : 0.f;      // unseen: exactly 0 whatever m is
+                sum += pr;
+                pf[r >> 3][r & 7] = (f16)pr;
+            }
+            l = fmaf(l, a, sum);
+            if (__any(moved)) {
+#pragma unroll
+                for (int db = 0; db < DB; ++db)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[db][r] *= a;
+            }
+            // ---- O^T[d][q] += V^T[d][slot] P^T[slot][q], k-slots as in the body file ----
+#pragma unroll
+            for (int db = 0; db < DB; ++db) {
+                const f16* vp = wV + tr_off + db * 32;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const f16x4 vl = lds_read_tr4(vp + (u * 16) * VSTR), vh = lds_read_tr4(vp + (u * 16 + 8) * VSTR);
+                    const f16x8 vf = {vl[0], vl[1], vl[2], vl[3], vh[0], vh[1], vh[2], vh[3]};
+                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[u], o[db], 0, 0, 0);
+                }
+            }
+            // ---- the next tile into the slot, after this tile's last LDS read ----
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            tile_store();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            if (!more) break;
+            kt = nk;
+            rest &= rest - 1u;
+        }
+        l += __shfl_xor(l, 32, 64);
+        const float inv = 1.0f / l;
+        if (q0 + l31 < Tq) {
+            f16* op = out + (qbase + (size_t)(q0 + l31) * HW) * ldo + head * D;
+#pragma unroll
+            for (int db = 0; db < DB; ++db)
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd) {
+                    f16x4 w;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) w[e] = (f16)(o[db][4 * qd + e] * inv);
+                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;
+                }
+        }
+        tl = tl_next;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
+    }
+}
 #undef TL_SLOT
 
 // waves per workgroup: as many as keep a workgroup's LDS at or below 42 KB (D = 64) / 37 KB (D = 128), at least one
@@ -1594,6 +1829,48 @@ extern "C" int mofa_attn_temporal_stream_f16(const void* q, const void* k, const
         return launch_temporal_long<G, attn_temporal_stream_kernel<G::D, G::WPB>>(
             nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale,
             radius, anchor);
+    };
+    return head_dim == 64 ? launch(TemporalLongGeom<64, 1>{}) : launch(TemporalLongGeom<128, 1>{});
+}
+
+// the streaming walk for a frame shard (attn_temporal_stream_shard_kernel): Tq >= 1 query frames against 1 <= S <= 1024 key slots.
+//   radius >= 0   window mode: the contract and the refusals of mofa_attn_temporal_long_window_f16 with 1024 slots for 128;
+//                 key_mask must be NULL.  radius is clamped to S - 1 (two band frames lie no further apart), so that no frame
+//                 sum overflows
+//   radius == -1  dense mode: anchor, q_frame0 and band_frame0 must be 0; key_mask is host memory of ceil(S / 32) words, bit
+//                 j % 32 of word j / 32 = slot j exists, NULL = every slot; bits at and above S are ignored; an empty mask is
+//                 refused.  The kernel gets the window that hides nothing (radius 2^30; Tq above 2^30 is refused for it)
+// The words travel as kernel arguments in both modes (window: every slot below S): no device allocation, no copy.
+extern "C" int mofa_attn_temporal_stream_shard_f16(const void* q, const void* k, const void* v, void* out, int nclips, int Tq,
+                                                   int S, int HW, int heads, int head_dim, int ld, int ldkv, int ldo, float scale,
+                                                   int radius, int anchor, int q_frame0, int band_frame0,
+                                                   const uint32_t* key_mask, mofa_stream_t stream) {
+    if (!temporal_long_args_ok(q, k, v, out, nclips, S, HW, heads, head_dim, ld, ldkv, ldo, 1024)) return MOFA_EINVAL;
+    if (Tq < 1 || Tq > (1 << 30) || radius < -1) return MOFA_EINVAL;
+    if (radius >= 0) {
+        if (key_mask) return MOFA_EINVAL;
+        if (anchor < 0 || anchor > S || band_frame0 < 0 || band_frame0 > (1 << 30)) return MOFA_EINVAL;
+        if (q_frame0 < band_frame0 || (long long)q_frame0 + Tq > (long long)band_frame0 + (S - anchor)) return MOFA_EINVAL;
+        if (radius > S - 1) radius = S - 1;
+    } else {
+        if (anchor != 0 || q_frame0 != 0 || band_frame0 != 0) return MOFA_EINVAL;
+        radius = 1 << 30;
+    }
+    TemporalShardWords words;
+    uint32_t any = 0;
+    for (int w = 0; w < 32; ++w) {
+        const int n = S - 32 * w;                                   // slots of this word below S
+        const uint32_t below = n >= 32 ? 0xffffffffu : n > 0 ? (1u << n) - 1u : 0u;
+        words.w[w] = below ? (key_mask ? key_mask[w] : 0xffffffffu) & below : 0u;     // (words past ceil(S / 32) are not read)
+        any |= words.w[w];
+    }
+    if (any == 0) return MOFA_EINVAL;
+    const long long nseq = (long long)nclips * HW * heads;
+    const auto launch = [&](auto g) {
+        using G = decltype(g);
+        return launch_temporal_long<G, attn_temporal_stream_shard_kernel<G::D, G::WPB>>(
+            nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, Tq, S, HW, heads, ld, ldkv, ldo,
+            scale, radius, anchor, q_frame0, band_frame0, words);
     };
     return head_dim == 64 ? launch(TemporalLongGeom<64, 1>{}) : launch(TemporalLongGeom<128, 1>{});
 }

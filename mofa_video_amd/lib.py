@@ -107,6 +107,7 @@ PROTOTYPES = {
     "mofa_attn_temporal_long_window_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I, _P],
     "mofa_attn_temporal_stream_local_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],
     "mofa_attn_temporal_stream_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],
+    "mofa_attn_temporal_stream_shard_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I, _P, _P],
     "mofa_softmax_rows_f16": [_P, _I, _I, _I, _P],
     "mofa_gn_nparts": [_I, _I],
     "mofa_gn_partial_f16": [_P, _P, _I, _I, _I, _I, _P],

@@ -631,6 +631,49 @@ def attn_temporal_stream(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None,
     return out
 
 
+def attn_temporal_stream_shard(q, k, v, nclips, S, HW, heads, head_dim=64, scale=None, out=None, Tq=None, local=None, q_frame0=0,
+                               band_frame0=0, key_mask=None):
+    """the streaming walk for a frame shard past 128 key slots, through mofa_attn_temporal_stream_shard_f16: q holds Tq frames per
+    clip (Tq=None: S), k / v hold 1 <= S <= 1024 key slots per clip.  local=None is dense mode, ``attn_temporal_sharded`` for more
+    slots: every query sees every slot that exists; key_mask (a Python int, bit j = slot j exists; None = every slot) names them,
+    and the K / V rows of the others are never read.  local=(radius, anchor) is window mode, ``attn_temporal_window`` for more
+    slots: the slots are ``anchor`` anchor frames and the band frames from band_frame0 on, the queries are the global frames from
+    q_frame0 on and must lie in the band, K and V of every slot must be finite, and key_mask must be None (the gathered, padded
+    buffer has no per-query rule).  With every slot live, Tq == S and both frames 0 the bits are those of
+    ``attn_temporal_stream`` under the same ``local``."""
+    words, live = None, S
+    if local is None:
+        radius, anchor = -1, 0
+        if q_frame0 or band_frame0:
+            raise ValueError("dense mode (local=None) takes no q_frame0 / band_frame0: the slots of a gathered buffer are not a band")
+        if key_mask is not None:
+            m = int(key_mask)
+            if m < 0:
+                raise ValueError("key_mask must be a non-negative integer")
+            nw = (max(S, 1) + 31) // 32
+            words = (C.c_uint32 * nw)(*[(m >> (32 * w)) & 0xffffffff for w in range(nw)])       # (bits >= 32 nw are >= S: ignored)
+            live = bin(m & ((1 << max(S, 0)) - 1)).count("1")
+    else:
+        if key_mask is not None:
+            raise ValueError("window mode (local=(radius, anchor)) takes no key_mask: the gathered-key path of frame-sharded clips "
+                             "has no per-query mask")
+        radius, anchor = (int(x) for x in local)
+        if radius < 0:
+            raise ValueError(f"local=(radius, anchor) needs radius >= 0, got {radius}")
+    Tq = S if Tq is None else Tq
+    lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * Tq * HW, heads, head_dim, scale, out)
+    t0 = TIMER.start() if TIMER is not None else None
+    L.check(lib.mofa_attn_temporal_stream_shard_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, Tq, S, HW, heads, head_dim,
+                                                    _ld(q), _ld(k), _ld(out), scale, radius, anchor, int(q_frame0), int(band_frame0),
+                                                    words, L.stream_ptr()), "mofa_attn_temporal_stream_shard_f16")
+    if t0 is not None:
+        Cc = heads * head_dim
+        pairs = Tq * live if local is None else window_visible_keys(S, Tq, radius, anchor, int(q_frame0), int(band_frame0))
+        TIMER.stop("attn_temporal_stream_kernel", t0, flops=4.0 * pairs * Cc * nclips * HW,
+                   nbytes=4.0 * nclips * (Tq + live) * HW * Cc)
+    return out
+
+
 def softmax_rows_(x):
     lib = L.load()
     L.check(lib.mofa_softmax_rows_f16(L.ptr(x), x.shape[0], x.shape[1], _ld(x), L.stream_ptr()), "mofa_softmax_rows_f16")

@@ -19,6 +19,8 @@ Weights are replicated.  Exchanges inside one denoise step (RCCL over xGMI throu
       Under a temporal window on a FrameParallel built with ``window_keys=True`` instead: ``radius`` frames to and from each
       neighbour shard (batched p2p, "data") and the anchor frames from shard 0 (one broadcast, bulk) into a [anchor + band
       frames] buffer, K|V projected for those slots only, mofa_attn_temporal_long_window_f16 -- never run on more than one GPU
+      On either path a rank with more than 128 key slots (``stream_keys=True``) attends through
+      mofa_attn_temporal_stream_shard_f16; the exchange and the buffers are the same -- never run on more than one GPU
     * CFG combine: the two halves of one frame shard swap their noise predictions                 (pair group)
 and once per clip: all-gather of the final latents before the VAE decode, whose chunks are independent and are
 dealt round-robin to ALL ranks.  Everything per-frame (2-D convs, spatial norms/attention, FFs, the adapter warps,
@@ -325,11 +327,14 @@ class ThreadComm:
         return _Done()
 
 
+STREAM_KEY_SLOTS = 1024     # the most key slots of mofa_attn_temporal_stream_shard_f16 (``FrameParallel(stream_keys=True)``)
+
+
 # ---------------------------------------------------------------------------------------------------------
 class FrameParallel:
     """The per-rank object blocks consult (``Ctx.par``) when a clip's frames are sharded."""
 
-    def __init__(self, layout, comm, p2p=True, max_key_slots=32, window_keys=False):
+    def __init__(self, layout, comm, p2p=True, max_key_slots=32, window_keys=False, stream_keys=False):
         """max_key_slots: the most key slots (frame_ranks x largest shard) the temporal attention takes from the gathered
         buffer in place, 32 .. 128.  The default of 32 is the T <= 32 masked kernel; above it clips of up to that many frames
         may be sharded and their attention runs through mofa_attn_temporal_long_masked_f16 (``ops.attn_temporal_sharded``).
@@ -340,8 +345,17 @@ class FrameParallel:
         of gathering the clip, and attend through mofa_attn_temporal_long_window_f16.  The key slots of a rank, anchor + T_max + 2
         radius <= 128, bound what can be sharded, not the clip length and not ``max_key_slots``.  Dense attention on such an
         object is unchanged.  Nothing of this path has run on more than one GPU: it is checked over gloo on the CPU and on
-        virtual ranks (ThreadComm) on one GPU; its wire time is unmeasured."""
-        if isinstance(max_key_slots, bool) or not isinstance(max_key_slots, int) or not 32 <= max_key_slots <= 128:
+        virtual ranks (ThreadComm) on one GPU; its wire time is unmeasured.
+        stream_keys: opt in to more than 128 key slots on this frame shard, through mofa_attn_temporal_stream_shard_f16
+        (``ops.attn_temporal_stream_shard``, an online-softmax walk over the rank's key tiles): ``max_key_slots`` is then accepted
+        up to 1024 and ``window_plan`` allows anchor + T_max + 2 radius <= 1024.  Up to 128 slots such an object launches what it
+        launches without the keyword.  Like the window path, never run on more than one GPU."""
+        self.stream_keys = bool(stream_keys)
+        if self.stream_keys:
+            if isinstance(max_key_slots, bool) or not isinstance(max_key_slots, int) or not 32 <= max_key_slots <= STREAM_KEY_SLOTS:
+                raise ValueError(f"max_key_slots must be an integer in 32 .. {STREAM_KEY_SLOTS} with stream_keys=True, got "
+                                 f"{max_key_slots!r}")
+        elif isinstance(max_key_slots, bool) or not isinstance(max_key_slots, int) or not 32 <= max_key_slots <= 128:
             raise ValueError(f"max_key_slots must be an integer in 32 .. 128, got {max_key_slots!r}")
         self.max_key_slots = max_key_slots
         self.window_keys = bool(window_keys)
@@ -613,7 +627,12 @@ class FrameParallel:
             if anchor > first:
                 raise ValueError(f"window_plan: anchor {anchor} exceeds the {first} frames of shard 0: the anchor frames would come "
                                  "from more than one shard")
-            if anchor + lay.T_max + 2 * radius > 128:
+            if self.stream_keys:
+                if anchor + lay.T_max + 2 * radius > STREAM_KEY_SLOTS:
+                    raise ValueError(f"window_plan: anchor + T_max + 2 radius = {anchor} + {lay.T_max} + 2 x {radius} = "
+                                     f"{anchor + lay.T_max + 2 * radius} key slots exceed the streaming attention kernel's "
+                                     f"{STREAM_KEY_SLOTS}")
+            elif anchor + lay.T_max + 2 * radius > 128:
                 raise ValueError(f"window_plan: anchor + T_max + 2 radius = {anchor} + {lay.T_max} + 2 x {radius} = "
                                  f"{anchor + lay.T_max + 2 * radius} key slots exceed the attention kernel's 128")
             b0, b1 = max(self.f0 - radius, 0), min(self.f1 + radius, lay.T)
@@ -693,15 +712,16 @@ class GroupedWindowParallel:
     hands every rank every stepped window (the g ranks of a group hold identical copies; entry 0 of each group is used).
     ``window_layout_costs`` says when this beats the two plain layouts (e.g. 4 windows on 8 ranks: 4 x 2)."""
 
-    def __init__(self, comm, rank, world, ranks_per_group, window_size, max_key_slots=32, window_keys=False):
+    def __init__(self, comm, rank, world, ranks_per_group, window_size, max_key_slots=32, window_keys=False, stream_keys=False):
         g = ranks_per_group
         assert world % g == 0 and g >= 2 and g % 2 == 0
         self.comm, self.rank, self.world, self.g = comm, rank, world, g
         self.groups, self.slot = world // g, rank // g
         self.frame = FrameParallel(Layout(g, rank % g, window_size, base=self.slot * g), comm, max_key_slots=max_key_slots,
-                                   window_keys=window_keys)
+                                   window_keys=window_keys, stream_keys=stream_keys)
         self.max_key_slots = self.frame.max_key_slots               # (what pipeline._check_call asks a ``parallel`` object for)
         self.window_keys = self.frame.window_keys
+        self.stream_keys = self.frame.stream_keys
 
     @staticmethod
     def layout_of_rank(world, ranks_per_group, window_size):

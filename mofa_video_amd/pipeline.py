@@ -184,7 +184,11 @@ class FlowControlNetPipeline:
         Nothing at full geometry has been run above 128 frames, and the memory of such a pass was not examined.
         Above the default of 32 the temporal attention runs through mofa_attn_temporal_long_f16; clips
         sharded over ranks (``parallel``) stay limited to 32 unless the parallel object was built with ``max_key_slots=`` (up
-        to 128): then to the smaller of the two.
+        to 128): then to the smaller of the two.  A sharded clip of more than 128 frames (up to the 256 admitted above) needs a
+        parallel object built with ``stream_keys=True`` and, dense, ``max_key_slots`` at least the clip's frames: a rank's
+        attention over more than 128 key slots then runs through mofa_attn_temporal_stream_shard_f16.  That path was run on
+        one GPU only (virtual ranks, small geometry, and a rank's call alone at level-0 geometry); nothing ran on more than one
+        GPU, no sharded clip of more than 128 frames ran at full geometry, and memory was not examined.
         temporal_window: None (dense temporal attention, the default: today's launches), an integer radius, or (radius,
         anchor): local temporal attention in every temporal layer of the UNet and the adapters -- query frame i sees key
         frame j iff j < anchor or |i - j| <= radius (mofa_attn_temporal_long_local_f16); an integer means (radius, 1), frame 0
@@ -193,7 +197,8 @@ class FlowControlNetPipeline:
         ``window_keys=True``: every rank then exchanges ``radius`` frames with its neighbour shards and takes the anchor frames
         from shard 0 instead of gathering the clip, and attends through mofa_attn_temporal_long_window_f16.  The key slots of a
         rank, anchor + largest shard + 2 radius <= 128, then take the place of ``max_key_slots`` (``FrameParallel.window_plan``
-        names the rule a layout breaks); ``max_temporal_frames`` still caps the frames of a forward pass.  That path has been
+        names the rule a layout breaks; a parallel object built with ``stream_keys=True`` as well takes up to 1024 slots, through
+        mofa_attn_temporal_stream_shard_f16 above 128); ``max_temporal_frames`` still caps the frames of a forward pass.  That path has been
         checked over gloo on the CPU and on virtual ranks on one GPU; nothing was run on more than one GPU.  Nothing is
         claimed about what the released checkpoints produce under a window."""
         self.temporal_window = _temporal_window(temporal_window)
@@ -390,15 +395,24 @@ class FlowControlNetPipeline:
             fpar = getattr(self.parallel, "frame", self.parallel)
             if fpar.lay.T != frames_per_forward:
                 raise ValueError(f"{frames_per_forward} frames per forward pass, but the parallel object's layout shards {fpar.lay.T}")
-            fpar.window_plan(*self.temporal_window)
+            try:
+                fpar.window_plan(*self.temporal_window)
+            except ValueError as e:             # past 128 key slots: name the keyword that lifts the limit (to 1024)
+                if getattr(fpar, "stream_keys", False) or "exceed the attention kernel's 128" not in str(e):
+                    raise
+                raise ValueError(f"{e} (a parallel object built with stream_keys=True takes up to 1024 key slots)") from None
         elif self.parallel is not None:
             slots = getattr(self.parallel, "max_key_slots", MAX_TEMPORAL_FRAMES)
             if frames_per_forward > slots and slots == MAX_TEMPORAL_FRAMES:
                 raise ValueError(f"{frames_per_forward} frames per forward pass with parallel=...: clips sharded over ranks are limited "
                                  f"to {MAX_TEMPORAL_FRAMES} frames (their gathered keys carry a 32-bit mask); run long clips on one device")
             if frames_per_forward > slots:
+                hint = ""
+                if frames_per_forward > MAX_TEMPORAL_FRAMES_LONG and not getattr(self.parallel, "stream_keys", False):
+                    hint = (f" (more than {MAX_TEMPORAL_FRAMES_LONG} frames: build it with stream_keys=True and max_key_slots >= "
+                            f"{frames_per_forward})")
                 raise ValueError(f"{frames_per_forward} frames per forward pass with parallel=...: this parallel object takes clips of "
-                                 f"at most max_key_slots = {slots} frames")
+                                 f"at most max_key_slots = {slots} frames" + hint)
 
     def prepare_latents(self, batch_size, num_frames, num_channels_latents, height, width, generator, latents=None):
         shape = (batch_size, num_frames, num_channels_latents // 2, height // 8, width // 8)
