@@ -177,7 +177,9 @@ int mofa_attn_spatial_qb_f16(const void* q, const void* k, const void* v, void* 
                              int nframes, int heads, int head_dim, int S, int ldq, int ldk, int ldv, int ldo, float scale,
                              int query_blocks, mofa_stream_t stream);
 /* [tokens][ld] columns in blocks of 64 (ncb = C/64 blocks) -> vt[((frame*ncb + cb)*64 + d)*S + key] = [frame][C][S]: the
- * weight operand of the VAE mid-block attention's second implicit GEMM (vae.py); the attention kernels do not need it */
+ * weight operand of the VAE mid-block attention's second implicit GEMM (vae.py); the attention kernels do not need it.
+ * S % 8 == 0 (any S: the last block of 64 keys may be ragged), ldv % 8 == 0, ldv >= ncb * 64; ncb and nframes are grid
+ * dimensions, at most 65535 each.  MOFA_EINVAL otherwise, before any device call. */
 int mofa_transpose_v_f16(const void* v, void* vt, int nframes, int ncb, int S, int ldv, mofa_stream_t stream);
 /* temporal self-attention over T frames per (clip, pixel, head), head_dim 64 or 128, T <= 32.
  * k/v: token row of (clip b, frame t, pixel p) = (b*T + t)*HW + p, leading dim ldkv.
@@ -305,7 +307,9 @@ int mofa_attn_temporal_stream_shard_f16(const void* q, const void* k, const void
                                         int nclips, int Tq, int S, int HW, int heads, int head_dim, int ld, int ldkv, int ldo,
                                         float scale, int radius, int anchor, int q_frame0, int band_frame0,
                                         const uint32_t* key_mask, mofa_stream_t stream);
-/* in-place row softmax of an fp16 [rows][cols] matrix (VAE mid-block attention, 1 head x 512) */
+/* in-place row softmax of an fp16 [rows][cols] matrix (VAE mid-block attention, 1 head x 512): fp32 maximum, exponentials
+ * and sum, one rounding to fp16 (subnormal results kept).  cols % 8 == 0, ld % 8 == 0, ld >= cols, x 16-byte aligned; any
+ * number of columns (a row is walked in passes of 2048), one workgroup per row.  MOFA_EINVAL otherwise, before any device call. */
 int mofa_softmax_rows_f16(void* x, int rows, int cols, int ld, mofa_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -459,7 +463,10 @@ int mofa_silu_f32(const float* x, float* y, int n, mofa_stream_t stream);
 /* fp32 -> fp16 / fp16 -> fp32 contiguous casts */
 int mofa_cast_f32_to_f16(const float* x, void* y, int64_t n, mofa_stream_t stream);
 int mofa_cast_f16_to_f32(const void* x, float* y, int64_t n, mofa_stream_t stream);
-/* NCHW fp32 [n][C][H][W] * scale -> token-major fp16 [n][H*W][ldo] (channels >= C left untouched) and back */
+/* NCHW fp32 [n][C][H][W] * scale -> token-major fp16 [n][H*W][ldo] (channels >= C left untouched) and back.  The value is
+ * one fp32 product rounded once to fp16 (back: the fp16 value as fp32).  Any C, HW >= 1 (tiles of 32 channels x 32 pixels,
+ * ragged edges masked); ldo / ldx >= C, no alignment asked; the image count n is a grid dimension, at most 65535 (and
+ * C <= 32 * 65535).  MOFA_EINVAL otherwise, before any device call. */
 int mofa_nchw_f32_to_nhwc_f16(const float* x, void* y, int n, int C, int HW, int ldo, float scale,
                               mofa_stream_t stream);
 int mofa_nhwc_f16_to_nchw_f32(const void* x, float* y, int n, int C, int HW, int ldx, mofa_stream_t stream);
@@ -569,7 +576,9 @@ int mofa_flow_downscale_f32(const float* flow, float* out, int n, int H, int W, 
  * Scheduler math (pipeline/pipeline.py:449-452, :495-500; utils/scheduling_euler_discrete_karras_fix.py:264-288, :418-528)
  * ---------------------------------------------------------------------------------------- */
 /* model input: out[2][T][HW][ldo] fp16: cols 0..3 = latents/sqrt(sigma^2+1) (both CFG halves),
- * cols 4..7 = image_latents[half] ; latents fp32 [T][4][HW] (NCHW), image_latents fp32 [2][4][HW] */
+ * cols 4..7 = image_latents[half] ; latents fp32 [T][4][HW] (NCHW), image_latents fp32 [2][4][HW].  The latent columns are
+ * one fp32 product with fl32(1/sqrt(sigma^2+1)) rounded once to fp16; columns >= 8 of a row are left untouched.
+ * T, HW >= 1, ldo % 8 == 0, ldo >= 8 (and for the step below ldn % 4 == 0, sigma > 0), MOFA_EINVAL otherwise. */
 int mofa_prepare_model_input(const float* latents, const float* image_latents, void* out,
                              int T, int HW, int ldo, float sigma, mofa_stream_t stream);
 /* CFG + v-prediction Euler step, fp32 latents in place.

@@ -791,6 +791,7 @@ __global__ __launch_bounds__(256) void transpose_v_kernel(const f16* __restrict_
 extern "C" int mofa_transpose_v_f16(const void* v, void* vt, int nframes, int heads, int S, int ldv,
                                     mofa_stream_t stream) {
     if (!v || !vt || nframes <= 0 || heads <= 0 || S <= 0 || S % 8 != 0 || ldv % 8 != 0) return MOFA_EINVAL;
+    if (nframes > 65535 || heads > 65535 || ldv < heads * 64) return MOFA_EINVAL;       // grid.z / grid.y; the row holds every block
     dim3 grid(cdiv(S, 64), heads, nframes);
     hipLaunchKernelGGL(transpose_v_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const f16*)v, (f16*)vt, heads, S,
                        ldv);
@@ -1911,7 +1912,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(f16* __restrict__ x, 
 }
 
 extern "C" int mofa_softmax_rows_f16(void* x, int rows, int cols, int ld, mofa_stream_t stream) {
-    if (!x || rows <= 0 || cols <= 0 || cols % 8 != 0 || ld % 8 != 0) return MOFA_EINVAL;
+    if (!x || rows <= 0 || cols <= 0 || cols % 8 != 0 || ld % 8 != 0 || ld < cols) return MOFA_EINVAL;
     hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (f16*)x, cols, ld);
     MOFA_CHECK_LAUNCH();
     return MOFA_OK;

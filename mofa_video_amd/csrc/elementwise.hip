@@ -7,6 +7,16 @@ static inline int ew_blocks(long long n) {
     return (int)(nb > 16384 ? 16384 : (nb < 1 ? 1 : nb));
 }
 
+// (f16)(a * b) with the product rounded to fp32 FIRST, as include/mofa_hip.h states it for the layout mover and the model input.
+// Left to contraction the compiler picks v_fma_mixlo_f16 for some of the elements: the exact product rounded once, which gives
+// other bits where the fp32 product is an fp16 tie, and -0 * s + 0 = +0.  (The instruction selector folds the conversion
+// into the product whatever the contraction setting is; the empty asm makes the fp32 product a value of its own.)
+__device__ __forceinline__ f16 mul_f32_to_f16(float a, float b) {
+    float p = a * b;
+    asm volatile("" : "+v"(p));
+    return (f16)p;
+}
+
 // y = a*x + b*y
 __global__ __launch_bounds__(256) void axpby_kernel(const f16* __restrict__ x, f16* __restrict__ y, long long nvec, int CV,
                                                     int ldx, int ldy, float a, float b) {
@@ -144,12 +154,13 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
     __syncthreads();
     for (int r = ty; r < 32; r += 8) {
         const int p = p0 + r, c = c0 + tx;
-        if (p < HW && c < C) y[((size_t)n * HW + p) * ldo + c] = (f16)(tile[tx][r] * scale);
+        if (p < HW && c < C) y[((size_t)n * HW + p) * ldo + c] = mul_f32_to_f16(tile[tx][r], scale);
     }
 }
 extern "C" int mofa_nchw_f32_to_nhwc_f16(const float* x, void* y, int n, int C, int HW, int ldo, float scale,
                                          mofa_stream_t stream) {
     if (!x || !y || n <= 0 || C <= 0 || HW <= 0 || ldo < C) return MOFA_EINVAL;
+    if (n > 65535 || cdiv(C, 32) > 65535) return MOFA_EINVAL;       // grid.z / grid.y
     dim3 grid(cdiv(HW, 32), cdiv(C, 32), n);
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, (f16*)y, C, HW, ldo, scale);
     MOFA_CHECK_LAUNCH();
@@ -172,6 +183,7 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const f16* __restrict
 }
 extern "C" int mofa_nhwc_f16_to_nchw_f32(const void* x, float* y, int n, int C, int HW, int ldx, mofa_stream_t stream) {
     if (!x || !y || n <= 0 || C <= 0 || HW <= 0 || ldx < C) return MOFA_EINVAL;
+    if (n > 65535 || cdiv(C, 32) > 65535) return MOFA_EINVAL;       // grid.z / grid.y
     dim3 grid(cdiv(HW, 32), cdiv(C, 32), n);
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const f16*)x, y, C, HW, ldx);
     MOFA_CHECK_LAUNCH();
@@ -234,7 +246,7 @@ __global__ void prepare_model_input_kernel(const float* __restrict__ lat, const 
         f16x8 o;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            o[c] = (f16)(lat[((size_t)t * 4 + c) * HW + p] * inv);
+            o[c] = mul_f32_to_f16(lat[((size_t)t * 4 + c) * HW + p], inv);
             o[4 + c] = (f16)img[((size_t)half * 4 + c) * HW + p];
         }
         *(f16x8*)(out + (size_t)i * ldo) = o;

@@ -19,6 +19,20 @@ def _res(s):
     return SpatioTemporalResBlock(s, eps=1e-6, temporal_eps=1e-5, switch=True)
 
 
+def mid_attention_core(q, k, v, nframes, S):
+    """single-head attention per frame over fp16 q, k, v [nframes*S, C] -> o [nframes*S, C], scores materialised"""
+    Cc = q.shape[1]
+    vt = ops.transpose_v(v, nframes, Cc // 64, S)                       # [nframes*C, S] = V^T per frame
+    o = torch.empty((nframes * S, Cc), dtype=torch.float16, device=q.device)
+    scale = 1.0 / math.sqrt(Cc)
+    for f in range(nframes):                                             # scores materialised per frame
+        rows = slice(f * S, (f + 1) * S)
+        p = ops.igemm(q[rows], k[rows].contiguous(), s_acc=scale)        # [S, S] = Q K^T / sqrt(d)
+        ops.softmax_rows_(p)
+        ops.igemm(p, vt[f * Cc:(f + 1) * Cc], out=o[rows])               # P V
+    return o
+
+
 class _MidAttention:
     """diffusers Attention(heads=1, dim_head=512, group norm 32 eps 1e-6, bias, residual_connection)."""
 
@@ -34,14 +48,7 @@ class _MidAttention:
         assert S % 64 == 0 and Cc % 64 == 0
         h = self.norm(x, nframes, S)
         q, k, v = self.to_q(h), self.to_k(h), self.to_v(h)
-        vt = ops.transpose_v(v, nframes, Cc // 64, S)                   # [nframes*C, S] = V^T per frame
-        o = torch.empty((nframes * S, Cc), dtype=torch.float16, device=x.device)
-        scale = 1.0 / math.sqrt(Cc)
-        for f in range(nframes):                                         # scores materialised per frame
-            rows = slice(f * S, (f + 1) * S)
-            p = ops.igemm(q[rows], k[rows].contiguous(), s_acc=scale)    # [S, S] = Q K^T / sqrt(d)
-            ops.softmax_rows_(p)
-            ops.igemm(p, vt[f * Cc:(f + 1) * Cc], out=o[rows])           # P V
+        o = mid_attention_core(q, k, v, nframes, S)
         return self.to_out(o, r1=x, s1=1.0, s_acc=self.s)
 
 

@@ -42,7 +42,8 @@ TOL = {
 }
 
 # arguments an op writes whatever the case (an ``out`` / ``ln_out`` buffer is added where a case passes one)
-WRITES = {"axpby_": ("y",), "axpby_f32_": ("y",), "copy2d": ("dst",), "softmax_rows_": ("x",), "gn_partial_into": ("part_rows",)}
+WRITES = {"axpby_": ("y",), "axpby_f32_": ("y",), "copy2d": ("dst",), "softmax_rows_": ("x",), "gn_partial_into": ("part_rows",),
+          "cfg_euler_step_": ("latents",), "cfg_euler_step_dev_": ("latents",)}
 EW_GRID_ITEMS = 16384 * 256      # csrc/elementwise.hip ew_blocks: more items than this and the grid-stride loop runs a second pass
 
 
