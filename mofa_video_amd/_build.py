@@ -16,7 +16,8 @@ PROBE_LIB = os.path.join(HERE, "..", "tools", "libmofa_hip_probe.so")
 SOURCES = ["igemm.hip", "igemm8.hip", "igemm320.hip", "ff320.hip", "lin320.hip", "attention.hip", "norm.hip", "elementwise.hip", "softsplat.hip", "output.hip",
            "cmp_ops.hip", "frontend.hip", "landmarks.hip", "control.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "igemm_common.h"), os.path.join(CSRC, "igemm_pipe.h"), os.path.join(CSRC, "igemm_plan.h"),
-           os.path.join(CSRC, "attn_temporal_long_body.inc"), os.path.join(CSRC, "landmarks_raster.h"), os.path.join(CSRC, "control_points.h"), os.path.join(HERE, "..", "include", "mofa_hip.h")]
+           os.path.join(CSRC, "attn_temporal_long_body.inc"), os.path.join(CSRC, "attn_temporal_stream_body.inc"),
+           os.path.join(CSRC, "landmarks_raster.h"), os.path.join(CSRC, "control_points.h"), os.path.join(HERE, "..", "include", "mofa_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 

@@ -23,10 +23,7 @@ from . import ops
 from .weights import (f32, fold_up2, interleave_geglu, pack_conv3d_t3, pack_conv3x3, pack_ff320, pack_lin320, pack_linear, pad_rows)
 
 BIG = 1 << 30
-# local temporal attention (Ctx.local): clips of up to this many frames go to ops.attn_temporal_local, whose kernel stages the
-# whole clip's keys; longer ones to ops.attn_temporal_local_stream (four key tiles in a ring, radius and anchor <= 32) or, under a
-# window beyond the ring's limits, to ops.attn_temporal_stream (an online-softmax walk over the visible key tiles)
-LOCAL_STREAM_ABOVE = 128
+LOCAL_STREAM_ABOVE = 128          # local temporal attention (Ctx.local) over longer clips streams its keys: see _local_attn
 RING_RADIUS = RING_ANCHOR = 32
 # frame-sharded clips: a rank's attention over more than this many key slots goes to ops.attn_temporal_stream_shard, on a parallel
 # object built with stream_keys=True (without the keyword such a slot count is refused before a block runs, or compacted)
@@ -37,6 +34,19 @@ def _stream_keys(par, slots):
     """whether a frame shard's temporal attention over ``slots`` key slots takes the streaming entry: up to 128 slots every
     object launches what it launched before the keyword existed"""
     return slots > SHARD_STREAM_ABOVE and bool(getattr(par, "stream_keys", False))
+
+
+def _sharded_attn(par, slots, window=False):
+    """the op (looked up on ``ops`` at the call) of a frame shard's temporal attention over ``slots`` key slots, dense or window"""
+    return ops.attn_temporal_stream_shard if _stream_keys(par, slots) else ops.attn_temporal_window if window else ops.attn_temporal_sharded
+
+
+def _local_attn(T, local):
+    """the op (looked up on ``ops`` at the call) of local temporal attention over whole clips of T frames: the kernel that stages the whole
+    clip's keys; past LOCAL_STREAM_ABOVE frames four key tiles in a ring or, under a window beyond the ring's limits, the walk over the visible tiles"""
+    if T <= LOCAL_STREAM_ABOVE:
+        return ops.attn_temporal_local
+    return ops.attn_temporal_local_stream if local[0] <= RING_RADIUS and local[1] <= RING_ANCHOR else ops.attn_temporal_stream
 
 
 class Sub:
@@ -511,13 +521,7 @@ class TransformerSpatioTemporal:
             if c.local is None:
                 a = ops.attn_temporal(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim)
             else:
-                if T <= LOCAL_STREAM_ABOVE:
-                    local = ops.attn_temporal_local
-                elif c.local[0] <= RING_RADIUS and c.local[1] <= RING_ANCHOR:
-                    local = ops.attn_temporal_local_stream
-                else:
-                    local = ops.attn_temporal_stream
-                a = local(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim, local=c.local)
+                a = _local_attn(T, c.local)(q, k, v, B, T, HW, self.heads, head_dim=self.tattn1.head_dim, local=c.local)
         elif c.local is not None:
             # local temporal attention on a frame shard (par.window_keys): this rank's queries see their band and the anchor
             # frames only, so the key buffer holds anchor + T + 2 radius frames at most instead of the clip.  LayerNorm writes
@@ -532,9 +536,8 @@ class TransformerSpatioTemporal:
             q = self.tattn1.q(fn)
             work.wait()
             kv = ops.igemm(hid, self.tattn1.wqkv[Cc:])
-            window = ops.attn_temporal_stream_shard if _stream_keys(par, wplan.S) else ops.attn_temporal_window
-            a = window(q, kv[:, :Cc], kv[:, Cc:], 1, wplan.S, HW, self.heads, head_dim=self.tattn1.head_dim,
-                       Tq=T, local=c.local, q_frame0=par.f0, band_frame0=wplan.b0)
+            a = _sharded_attn(par, wplan.S, window=True)(q, kv[:, :Cc], kv[:, Cc:], 1, wplan.S, HW, self.heads, head_dim=self.tattn1.head_dim,
+                                                         Tq=T, local=c.local, q_frame0=par.f0, band_frame0=wplan.b0)
         else:
             # this rank holds T of the clip's T_full frames.  The K|V projection writes this shard's slot of the gather
             # buffer, one all_gather_into_tensor (asynchronous, RCCL's stream) fills the other slots while the Q
@@ -553,9 +556,8 @@ class TransformerSpatioTemporal:
                 q = self.tattn1.q(fn)
                 work.wait()
                 kv = ops.igemm(hid, self.tattn1.wqkv[Cc:])
-                sharded = ops.attn_temporal_stream_shard if _stream_keys(par, par.kv_slots) else ops.attn_temporal_sharded
-                a = sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
-                            head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
+                a = _sharded_attn(par, par.kv_slots)(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
+                                                     head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
             elif par.kv_slots <= par.max_key_slots and par.kv_inplace:
                 fn = fn if fn is not None else self.tnorm1(f)
                 kv, own = par.kv_buffer(HW, 2 * Cc, fn.device)
@@ -563,9 +565,8 @@ class TransformerSpatioTemporal:
                 work = par.kv_gather_begin(kv, HW)
                 q = self.tattn1.q(fn)
                 work.wait()
-                sharded = ops.attn_temporal_stream_shard if _stream_keys(par, par.kv_slots) else ops.attn_temporal_sharded
-                a = sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
-                            head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
+                a = _sharded_attn(par, par.kv_slots)(q, kv[:, :Cc], kv[:, Cc:], 1, par.kv_slots, HW, self.heads,
+                                                     head_dim=self.tattn1.head_dim, Tq=T, key_mask=par.kv_mask)
             else:   # more than par.max_key_slots slots after padding (31 frames over 3 shards; 128 over 3 at a limit of 128), or the in-place path failed
                     # its self-check on this transport (parallel.FrameParallel.self_check): compact to T_full frames
                 fn = fn if fn is not None else self.tnorm1(f)
@@ -574,8 +575,7 @@ class TransformerSpatioTemporal:
                 ops.copy2d(k, kv[:, :Cc])
                 ops.copy2d(v, kv[:, Cc:])
                 kv = par.gather_frames(kv, HW)
-                sharded = ops.attn_temporal_stream_shard if _stream_keys(par, par.T_full) else ops.attn_temporal_sharded
-                a = sharded(q, kv[:, :Cc], kv[:, Cc:], 1, par.T_full, HW, self.heads, head_dim=self.tattn1.head_dim, Tq=T)
+                a = _sharded_attn(par, par.T_full)(q, kv[:, :Cc], kv[:, Cc:], 1, par.T_full, HW, self.heads, head_dim=self.tattn1.head_dim, Tq=T)
         # temporal cross-attention row vector.  diffusers 0.24.0 quirk: token row (b, s) of the GLOBAL batch takes the
         # context of batch (b*HW + s) mod B_global; v_tm has one row per global batch element.
         Bg = v_tm.shape[0]

@@ -23,6 +23,7 @@
 //   mofa_attn_temporal_stream_f16: any radius and anchor, dense included, 1 <= T <= 1024: an online-softmax walk over the key tiles.
 //   mofa_attn_temporal_stream_shard_f16: that walk for a frame shard, Tq query frames against 1 <= S <= 1024 key slots: the window
 //   rule on anchor + band slots, or dense under a key mask whose dead slots are never read.
+//   One body (attn_temporal_stream_body.inc) included by the two walks; the ring kernel shares their decode, Q load, store and tile.
 //
 // mofa_transpose_v_f16, mofa_softmax_rows_f16: the two helpers of the VAE mid-block attention (scores materialised by implicit GEMMs).
 
@@ -1090,6 +1091,45 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_long_window_kernel(con
 // of tiles past the last hold zeros or an earlier, finite tile.  Precondition as for the local kernel: K and V of all T frames
 // are finite.  Query rows >= T are neither loaded nor stored.
 // ---------------------------------------------------------------------------------------------------
+// What the three streaming kernels (this one and the two walks below) share outside their block loops, as text: as
+// __forceinline__ functions -- the fragments by reference or in a returned struct -- each of the three changed the instructions
+// of every kernel that called it.
+// one wave per sequence: the wave's lanes (query l31, half lh) and its sequence (clip b, pixel p, head); a workgroup's last waves
+// may have none and leave (no workgroup barrier follows: LDS regions are per wave); wK / wV: the wave's LDS region of ROWS key rows
+#define TEMPORAL_WAVE_DECODE(ROWS)                                 \
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6; \
+    const long long seq = (long long)blockIdx.x * WPB + wave;      \
+    if (seq >= nseq) return;                                       \
+    const int l31 = lane & 31, lh = lane >> 5;                     \
+    const int head = (int)(seq % heads);                           \
+    const long long bp = seq / heads;                              \
+    const int p = (int)(bp % HW);                                  \
+    const int b = (int)(bp / HW);                                  \
+    extern __shared__ __attribute__((aligned(16))) char smem_ts[]; \
+    f16* wK = (f16*)smem_ts + (size_t)wave * ((ROWS) * (2 * D + 40)); \
+    f16* wV = wK + (ROWS) * (D + 8);
+
+// Q fragments of the 32-query block of this lane's query row `row` (B operand of S^T): lane (query l31, half lh) holds
+// Q[row][16 kk + 8 lh .. + 8); rows >= Tq are not read and become zero
+#define TEMPORAL_LOAD_Q(qf, row, qbase, Tq)                                                                    \
+    {                                                                                                          \
+        const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};                                                          \
+        const int qi = (row);                                                                                  \
+        const f16* qp = q + ((qbase) + (size_t)(qi < (Tq) ? qi : 0) * HW) * ld + head * D + lh * 8;            \
+        _Pragma("unroll") for (int kk = 0; kk < D / 16; ++kk) (qf)[kk] = qi < (Tq) ? *(const f16x8*)(qp + kk * 16) : zero8; \
+    }
+// O^T of this lane's query row `row`, times inv, to its token row; rows >= Tq are not stored
+#define TEMPORAL_STORE_O(o, inv, row, qbase, Tq)                                                               \
+    if ((row) < (Tq)) {                                                                                        \
+        f16* op = out + ((qbase) + (size_t)(row) * HW) * ldo + head * D;                                       \
+        _Pragma("unroll") for (int db = 0; db < D / 32; ++db)                                                  \
+            _Pragma("unroll") for (int qd = 0; qd < 4; ++qd) {                                                 \
+                f16x4 w;                                                                                       \
+                _Pragma("unroll") for (int e = 0; e < 4; ++e) w[e] = (f16)((o)[db][4 * qd + e] * (inv));       \
+                *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;                                                 \
+            }                                                                                                  \
+    }
+
 // one 32-row tile of K and V in flight between memory and its LDS slot: lane (r0, cc) holds the 16-byte chunk cc of the rows
 // r0, r0 + RPI, ...
 template <int D>
@@ -1132,26 +1172,11 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_local_kernel(co
                                                                               int anchor) {
     constexpr int KK = D / 16, DB = D / 32, KSTR = D + 8, VSTR = D + 32;
     constexpr int NS = 4, ROWS = 32 * NS;                          // tile slots, rows of the wave's region
-    extern __shared__ __attribute__((aligned(16))) char smem_ts[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long seq = (long long)blockIdx.x * WPB + wave;
-    if (seq >= nseq) return;                                       // (no workgroup barrier below: LDS regions are per wave)
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int head = (int)(seq % heads);
-    const long long bp = seq / heads;
-    const int p = (int)(bp % HW);
-    const int b = (int)(bp / HW);
-    const size_t base = ((size_t)b * T * HW + p);                  // q / k / v / out token row of frame 0
-    f16* wK = (f16*)smem_ts + (size_t)wave * (ROWS * (KSTR + VSTR));
-    f16* wV = wK + ROWS * KSTR;
-    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    TEMPORAL_WAVE_DECODE(ROWS)
+    const size_t base = ((size_t)b * T * HW + p);              // q / k / v / out token row of frame 0
 
     f16x8 qf[KK];
-    {
-        const f16* qp = q + (base + (size_t)(l31 < T ? l31 : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) qf[kk] = l31 < T ? *(const f16x8*)(qp + kk * 16) : zero8;
-    }
+    TEMPORAL_LOAD_Q(qf, l31, base, T)
     // slot 0 <- tile 0, slot 2 <- tile 1, slots 1 and 3 <- zero (t_first = T: no row is read)
     {
         TemporalStreamTile<D> t0, t1, tz;
@@ -1178,12 +1203,7 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_local_kernel(co
         nt.load(k, v, base, HW, ldkv, head, T, q0 + 64, lane);
         // the next block's Q fragments are fetched under this block's arithmetic
         f16x8 qn[KK];
-        {
-            const int qi = q0 + 32 + l31;
-            const f16* qp = q + (base + (size_t)(qi < T ? qi : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) qn[kk] = qi < T ? *(const f16x8*)(qp + kk * 16) : zero8;
-        }
+        TEMPORAL_LOAD_Q(qn, q0 + 32 + l31, base, T)
         // the rule as four words, as in the local kernel: tile 0 with anchor and band; band tiles with the band alone, which is
         // empty by itself for a tile < 0 or >= ceil(T / 32) (lo >= 0, hi1 <= T) and is emptied for the band copy of tile 0
         unsigned ml[NS];
@@ -1257,18 +1277,7 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_local_kernel(co
         nt.store(wK + sa * 32 * KSTR, wV + sa * 32 * VSTR, lane);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
-        if (q0 + l31 < T) {
-            f16* op = out + (base + (size_t)(q0 + l31) * HW) * ldo + head * D;
-#pragma unroll
-            for (int db = 0; db < DB; ++db)
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    f16x4 w;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) w[e] = (f16)(o[db][4 * qd + e] * inv);
-                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;
-                }
-        }
+        TEMPORAL_STORE_O(o, inv, q0 + l31, base, T)
         const int s0 = sa;
         sa = sb; sb = sc; sc = s0;
 #pragma unroll
@@ -1278,186 +1287,53 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_local_kernel(co
 
 // ---------------------------------------------------------------------------------------------------
 // Streaming temporal attention under ANY window of the local rule, dense included: 1 <= T <= 1024 frames, radius >= 0 (the host
-// clamps it to T - 1), 0 <= anchor <= T.  One wave owns one sequence and ONE 32-row tile slot of K and V in LDS (the KT = 1
-// geometry: four waves a workgroup at D = 64, two at D = 128).  Per 32-query block q0 it walks, in ascending frame order and each
-// once, the key tiles that hold a key some query of the block can see
+// clamps it to T - 1), 0 <= anchor <= T.  The online-softmax walk of attn_temporal_stream_body.inc -- the body file says what a
+// wave keeps across the tiles, where the arithmetic's two hazards lie and how a tile travels -- over whole clips: per 32-query
+// block q0 it visits, in ascending frame order and each once, the key tiles that hold a key some query of the block can see
 //   anchor tiles  0 .. ceil(anchor / 32) - 1
 //   band tiles    (max(q0 - radius, 0) >> 5) .. (min(q0 + 31 + radius, T - 1) >> 5), those not among the anchor tiles
-// and never reads the others.  Across the tiles it keeps, per query, a running maximum m, this lane half's part l of the running
-// sum (the halves meet once, after the last tile) and the fp32 O^T accumulators; per tile
-//   m' = max(m, tile maximum over the VISIBLE keys)     a = exp2((m - m') c2)     l = a l + sum p     O^T = a O^T + V^T P^T
-// with p = exp2((s - m') c2) rounded to fp16 for P V, as in the long kernel, and one multiplication by 1 / l at the end.  a is set
-// to 1 where m' = m, and O^T is rescaled only where some lane's maximum moved (the skip changes no bit).
-// A hidden key's probability is SET to 0, not left to exp2: a visited tile can hide every key of a row whose maximum is still the
-// initial -1e30 (anchor = 0: the block's first band tile lies wholly below the band of its last queries whenever radius % 32 != 0),
-// and there exp2((s - m') c2) is exp2(+huge) = infinity (exp2(0) = 1 had the score been replaced by -1e30 first), which the
-// rescale by a = 0 at the row's first visible key turns into NaN.  With the select such a tile leaves m, l and O^T as they were.  Every row meets a
-// visible key in some visited tile (itself), so l > 0 at the end.
-// The walk is the same for a rule that hides nothing however it is spelt (radius >= T - 1, or anchor = T): all tiles, ascending,
-// every probability from exp2 -- equal bits.
-// The tile after the current one -- the next block's first tile after a block's last -- travels to registers under the current
-// tile's arithmetic and enters the slot behind the tile's last LDS read (s_waitcnt + wave barrier on both sides, as in the ring
-// kernel).  Frame rows >= T are not read (they are the next clip's) and are written as zero; K and V of all T frames must be
-// finite: a hidden frame of a visited tile is read and multiplied by its zero.  Query rows >= T take the rule of row T - 1 and
-// are neither loaded nor stored.  K and V of a sequence are read once per query block that sees them (from L2 after the first).
+// Every row meets a visible key in some visited tile (itself).  The walk is the same for a rule that hides nothing however it is
+// spelt (radius >= T - 1, or anchor = T): all tiles, ascending, every probability from exp2 -- equal bits.
+// Frame rows >= T are not read (they are the next clip's) and are written as zero; K and V of all T frames must be finite.  Query
+// rows >= T take the rule of row T - 1.  What stays here is what differs from the shard kernel: the clip strides, the rows of a
+// tile that are loaded, the lane's band and how the walk names its first and next tile (the body's seven macros).
 // ---------------------------------------------------------------------------------------------------
 template <int D, int WPB>
 __global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
                                                                         const f16* __restrict__ v, f16* __restrict__ out,
                                                                         long long nseq, int T, int HW, int heads, int ld,
                                                                         int ldkv, int ldo, float scale, int radius, int anchor) {
-    constexpr int KK = D / 16, DB = D / 32, KSTR = D + 8, VSTR = D + 32;
-    extern __shared__ __attribute__((aligned(16))) char smem_tsd[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long seq = (long long)blockIdx.x * WPB + wave;
-    if (seq >= nseq) return;                                       // (no workgroup barrier below: LDS regions are per wave)
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int head = (int)(seq % heads);
-    const long long bp = seq / heads;
-    const int p = (int)(bp % HW);
-    const int b = (int)(bp / HW);
-    const size_t base = ((size_t)b * T * HW + p);                  // q / k / v / out token row of frame 0
-    f16* wK = (f16*)smem_tsd + (size_t)wave * (32 * (KSTR + VSTR));
-    f16* wV = wK + 32 * KSTR;
-    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    TEMPORAL_WAVE_DECODE(32)
+    const int Tq = T;
+    const size_t base = ((size_t)b * T * HW + p), qbase = base;   // q / k / v / out token row of frame 0
     const int nA = (anchor + 31) >> 5;                             // anchor tiles
     const auto first_tile = [&](int q0) { return nA > 0 ? 0 : max(q0 - radius, 0) >> 5; };
-
-    f16x8 qf[KK];
-    {
-        const f16* qp = q + (base + (size_t)(l31 < T ? l31 : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) qf[kk] = l31 < T ? *(const f16x8*)(qp + kk * 16) : zero8;
-    }
-    {
-        TemporalStreamTile<D> t0;
-        t0.load(k, v, base, HW, ldkv, head, T, first_tile(0) * 32, lane);
-        t0.store(wK, wV, lane);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this wave's LDS writes are in place
-    __builtin_amdgcn_wave_barrier();
-
-    const float c2 = scale * 1.4426950408889634f;
-    const int tr_off = (((lane & 15) >> 2) + 4 * lh) * VSTR + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-#pragma unroll 1
-    for (int q0 = 0; q0 < T; q0 += 32) {
-        // the next block's Q fragments are fetched under this block's arithmetic
-        f16x8 qn[KK];
-        {
-            const int qi = q0 + 32 + l31;
-            const f16* qp = q + (base + (size_t)(qi < T ? qi : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) qn[kk] = qi < T ? *(const f16x8*)(qp + kk * 16) : zero8;
-        }
-        // the block's walk (wave-uniform): tiles 0 .. nA - 1, then band0 .. last
-        const int band0 = max(max(q0 - radius, 0) >> 5, nA);
-        const int last = max(min(q0 + 31 + radius, T - 1) >> 5, nA - 1);
-        // this lane's query and its band [lo, hi1)
-        const int qi = min(q0 + l31, T - 1);
-        const int lo = max(qi - radius, 0), hi1 = min(qi + radius, T - 1) + 1;
-
-        float m = -1e30f, mc = m * c2, l = 0.f;
-        f32x16 o[DB];
-#pragma unroll
-        for (int db = 0; db < DB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
-
-        int kt = nA > 0 ? 0 : band0;
-#pragma unroll 1
-        for (;;) {
-            int nk = kt + 1;
-            if (nk >= nA && nk < band0) nk = band0;
-            const bool more = nk <= last;
-            // the next tile of the walk travels to registers under this tile's arithmetic (after the last: nothing is read)
-            TemporalStreamTile<D> nt;
-            nt.load(k, v, base, HW, ldkv, head, T, more ? nk * 32 : q0 + 32 < T ? first_tile(q0 + 32) * 32 : T, lane);
-
-            const auto below = [](int n) { return (unsigned)((1ull << min(max(n, 0), 32)) - 1ull); };
-            const unsigned ml = (below(anchor - 32 * kt) | (below(hi1 - 32 * kt) & ~below(lo - 32 * kt))) >> (4 * lh);
-            // ---- S^T tile: s[r] = score(key = 32 kt + (r & 3) + 8 (r >> 2) + 4 lh, query = q0 + l31) ----
-            f32x16 s;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[r] = 0.f;
-            {
-                const f16* kp = wK + l31 * KSTR + lh * 8;
-#pragma unroll
-                for (int kk = 0; kk < KK; ++kk) {
-                    const f16x8 kf = *(const f16x8*)(kp + kk * 16);
-                    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], s, 0, 0, 0);
-                }
-            }
-            float mx = m;
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (ml & (1u << TL_SLOT(r))) mx = fmaxf(mx, s[r]);
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float mcn = mx * c2;
-            // a is SET to 1 where the maximum stayed: mc - mx c2 may be contracted into one fma, which returns the product's
-            // rounding error instead of 0 -- about 1e21 in size at m = -1e30, exp2 of which is 0 or infinity
-            const bool moved = mx != m;
-            const float a = moved ? __builtin_amdgcn_exp2f(mc - mcn) : 1.0f;   // m = -1e30 < mx: exp2(-huge) = 0
-            m = mx; mc = mcn;
-            float sum = 0.f;
-            f16x8 pf[2];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float e = __builtin_amdgcn_exp2f(fmaf(s[r], c2, -mc));
-                const float pr = (ml & (1u << TL_SLOT(r))) ? e : 0.f;      // hidden: exactly 0 whatever m is
-                sum += pr;
-                pf[r >> 3][r & 7] = (f16)pr;
-            }
-            l = fmaf(l, a, sum);
-            if (__any(moved)) {
-#pragma unroll
-                for (int db = 0; db < DB; ++db)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) o[db][r] *= a;
-            }
-            // ---- O^T[d][q] += V^T[d][key] P^T[key][q], k-slots as in the body file ----
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                const f16* vp = wV + tr_off + db * 32;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const f16x4 vl = lds_read_tr4(vp + (u * 16) * VSTR), vh = lds_read_tr4(vp + (u * 16 + 8) * VSTR);
-                    const f16x8 vf = {vl[0], vl[1], vl[2], vl[3], vh[0], vh[1], vh[2], vh[3]};
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[u], o[db], 0, 0, 0);
-                }
-            }
-            // ---- the next tile into the slot, after this tile's last LDS read ----
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            nt.store(wK, wV, lane);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            if (!more) break;
-            kt = nk;
-        }
-        l += __shfl_xor(l, 32, 64);
-        const float inv = 1.0f / l;
-        if (q0 + l31 < T) {
-            f16* op = out + (base + (size_t)(q0 + l31) * HW) * ldo + head * D;
-#pragma unroll
-            for (int db = 0; db < DB; ++db)
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    f16x4 w;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) w[e] = (f16)(o[db][4 * qd + e] * inv);
-                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;
-                }
-        }
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
-    }
+#define TS_FIRST(t0) t0.load(k, v, base, HW, ldkv, head, T, first_tile(0) * 32, lane);
+// the block's walk: tiles 0 .. nA - 1, then band0 .. last; this lane's query qi and its band
+#define TS_BLOCK(q0)                                                                  \
+    const int band0 = max(max((q0) - radius, 0) >> 5, nA);                            \
+    const int last = max(min((q0) + 31 + radius, T - 1) >> 5, nA - 1);                \
+    const int qi = min((q0) + l31, T - 1);                                            \
+    const int lo = max(qi - radius, 0), hi1 = min(qi + radius, T - 1) + 1;
+#define TS_START int kt = nA > 0 ? 0 : band0;
+#define TS_NEXT(nt)                                                                   \
+    int nk = kt + 1;                                                                  \
+    if (nk >= nA && nk < band0) nk = band0;                                           \
+    const bool more = nk <= last;                                                     \
+    TemporalStreamTile<D> nt;                                                         \
+    nt.load(k, v, base, HW, ldkv, head, T, more ? nk * 32 : q0 + 32 < T ? first_tile(q0 + 32) * 32 : T, lane); \
+    const auto below = [](int n) { return (unsigned)((1ull << min(max(n, 0), 32)) - 1ull); };
+#define TS_AND_WORD(kt)
+#define TS_ADVANCE kt = nk;
+#define TS_STORE(t) t.store(wK, wV, lane);
+#include "attn_temporal_stream_body.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------
 // The streaming walk on the key buffer of a FRAME SHARD: Tq query rows of a clip (clip stride Tq * HW in q / out) against
-// 1 <= S <= 1024 key SLOTS (clip stride S * HW in k / v).  The tile walk, the online softmax and the KT = 1 geometry are those of
-// attn_temporal_stream_kernel above (its header comment holds here, the -1e30 hazard and its select included); what differs is
-// which slots a query sees.  ONE rule serves both forms of a sharded clip, a slot being seen iff the window shows it AND it exists:
+// 1 <= S <= 1024 key SLOTS (clip stride S * HW in k / v).  The tile walk's step, the online softmax and the KT = 1 geometry are the
+// text of attn_temporal_stream_kernel: attn_temporal_stream_body.inc (its header holds here, the two hazards and their selects
+// included); what differs is which slots a query sees.  ONE rule serves both forms of a sharded clip, a slot being seen iff the window shows it AND it exists:
 //   window   slots [0, anchor) hold the global frames 0 .. anchor - 1, slot s >= anchor the global frame band_frame0 + (s - anchor);
 //            the query of global frame g = q_frame0 + row sees the anchor slots and the band slots [lo, hi1) of
 //            attn_temporal_long_window_kernel (frame >= anchor and within radius of g: a band slot that repeats an anchor frame
@@ -1492,22 +1368,9 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_shard_kernel(co
                                                                               int ld, int ldkv, int ldo, float scale, int radius,
                                                                               int anchor, int q_frame0, int band_frame0,
                                                                               TemporalShardWords words) {
-    constexpr int KK = D / 16, DB = D / 32, KSTR = D + 8, VSTR = D + 32;
-    constexpr int DC = D / 8, RPI = 64 / DC, NR = 32 / RPI;        // a tile in flight, as in TemporalStreamTile
-    extern __shared__ __attribute__((aligned(16))) char smem_tss[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long seq = (long long)blockIdx.x * WPB + wave;
-    if (seq >= nseq) return;                                       // (no workgroup barrier below: LDS regions are per wave)
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int head = (int)(seq % heads);
-    const long long bp = seq / heads;
-    const int p = (int)(bp % HW);
-    const int b = (int)(bp / HW);
-    const size_t base = ((size_t)b * S * HW + p);                  // k / v token row of slot 0
-    const size_t qbase = ((size_t)b * Tq * HW + p);                // q / out token row of the first query frame
-    f16* wK = (f16*)smem_tss + (size_t)wave * (32 * (KSTR + VSTR));
-    f16* wV = wK + 32 * KSTR;
-    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    TEMPORAL_WAVE_DECODE(32)
+    const size_t base = ((size_t)b * S * HW + p);              // k / v token row of slot 0
+    const size_t qbase = ((size_t)b * Tq * HW + p);            // q / out token row of the first query frame
     const auto below = [](int n) { return (unsigned)((1ull << min(max(n, 0), 32)) - 1ull); };
 
     // the 32 mask words in one register: lane j holds word j; exist = the tiles that hold a slot
@@ -1529,163 +1392,65 @@ __global__ __launch_bounds__(64 * WPB) void attn_temporal_stream_shard_kernel(co
         if (lo < hi1) t |= below(((hi1 - 1) >> 5) + 1) & ~below(lo >> 5);
         return t & exist;
     };
-    // one 32-row tile of K and V in flight between memory and the slot: rows of slots that do not exist (and every row under a
-    // zero word) are not read and become zero
-    f16x8 gk[NR], gv[NR];
+    // tile kt between memory and the slot: rows of slots that do not exist (bit i of w clear for row 32 kt + i; every row under a
+    // zero word) are not read and become zero.  The load and the store stay the kernel's own text: through TemporalStreamTile's,
+    // with a row predicate and the slot's pointers as arguments, the kernel compiles to other code
+    constexpr int DC = D / 8, RPI = 64 / DC, NR = 32 / RPI;
     const int r0 = lane / DC, cc = lane % DC;
-    const auto tile_load = [&](int kt, unsigned w) {
+    const auto tile_load = [&](TemporalStreamTile<D>& t, int kt, unsigned w) {
+        const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
             const int i = u * RPI + r0;
-            gk[u] = zero8; gv[u] = zero8;
+            t.gk[u] = zero8; t.gv[u] = zero8;
             if ((w >> i) & 1u) {
                 const size_t off = (base + (size_t)(kt * 32 + i) * HW) * ldkv + head * D + cc * 8;
-                gk[u] = *(const f16x8*)(k + off);
-                gv[u] = *(const f16x8*)(v + off);
+                t.gk[u] = *(const f16x8*)(k + off);
+                t.gv[u] = *(const f16x8*)(v + off);
             }
         }
     };
-    const auto tile_store = [&]() {
+    const auto tile_store = [&](const TemporalStreamTile<D>& t) {
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
             const int i = u * RPI + r0;
-            *(f16x8*)&wK[i * KSTR + cc * 8] = gk[u];
-            *(f16x8*)&wV[i * VSTR + cc * 8] = gv[u];
+            *(f16x8*)&wK[i * (D + 8) + cc * 8] = t.gk[u];
+            *(f16x8*)&wV[i * (D + 32) + cc * 8] = t.gv[u];
         }
     };
-
-    f16x8 qf[KK];
-    {
-        const f16* qp = q + (qbase + (size_t)(l31 < Tq ? l31 : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) qf[kk] = l31 < Tq ? *(const f16x8*)(qp + kk * 16) : zero8;
-    }
-    unsigned tl = tiles(0);
-    {
-        const int kt0 = __builtin_ctz(tl);
-        tile_load(kt0, word(kt0));
-        tile_store();
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this wave's LDS writes are in place
-    __builtin_amdgcn_wave_barrier();
-
-    const float c2 = scale * 1.4426950408889634f;
-    const int tr_off = (((lane & 15) >> 2) + 4 * lh) * VSTR + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-#pragma unroll 1
-    for (int q0 = 0; q0 < Tq; q0 += 32) {
-        // the next block's Q fragments are fetched under this block's arithmetic
-        f16x8 qn[KK];
-        {
-            const int qi = q0 + 32 + l31;
-            const f16* qp = q + (qbase + (size_t)(qi < Tq ? qi : 0) * HW) * ld + head * D + lh * 8;
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) qn[kk] = qi < Tq ? *(const f16x8*)(qp + kk * 16) : zero8;
-        }
-        const unsigned tl_next = q0 + 32 < Tq ? tiles(q0 + 32) : 0u;
-        // this lane's query and its band slots [lo, hi1) (lo >= hi1: a query below the anchor whose band lies inside it)
-        const int g = q_frame0 + min(q0 + l31, Tq - 1);
-        const int lo = anchor + max(max(g - radius, anchor), band_frame0) - band_frame0;
-        const int hi1 = anchor + min(g + radius, hi_f) - band_frame0 + 1;
-
-        float m = -1e30f, mc = m * c2, l = 0.f;
-        f32x16 o[DB];
-#pragma unroll
-        for (int db = 0; db < DB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
-
-        int kt = __builtin_ctz(tl);
-        unsigned rest = tl & (tl - 1u);
-#pragma unroll 1
-        for (;;) {
-            const bool more = rest != 0u;
-            // the next tile of the walk -- after a block's last, the next block's first -- travels to registers under this tile's
-            // arithmetic (after the last tile of all: a zero word, nothing is read)
-            const unsigned nxt = more ? rest : tl_next;
-            const int nk = nxt ? __builtin_ctz(nxt) : 0;
-            tile_load(nk, nxt ? word(nk) : 0u);
-
-            const unsigned ml =
-                ((below(anchor - 32 * kt) | (below(hi1 - 32 * kt) & ~below(lo - 32 * kt))) & word(kt)) >> (4 * lh);
-            // ---- S^T tile: s[r] = score(slot = 32 kt + (r & 3) + 8 (r >> 2) + 4 lh, query = q0 + l31) ----
-            f32x16 s;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[r] = 0.f;
-            {
-                const f16* kp = wK + l31 * KSTR + lh * 8;
-#pragma unroll
-                for (int kk = 0; kk < KK; ++kk) {
-                    const f16x8 kf = *(const f16x8*)(kp + kk * 16);
-                    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], s, 0, 0, 0);
-                }
-            }
-            float mx = m;
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (ml & (1u << TL_SLOT(r))) mx = fmaxf(mx, s[r]);
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float mcn = mx * c2;
-            // a is SET to 1 where the maximum stayed (see attn_temporal_stream_kernel)
-            const bool moved = mx != m;
-            const float a = moved ? __builtin_amdgcn_exp2f(mc - mcn) : 1.0f;   // m = -1e30 < mx: exp2(-huge) = 0
-            m = mx; mc = mcn;
-            float sum = 0.f;
-            f16x8 pf[2];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float e = __builtin_amdgcn_exp2f(fmaf(s[r], c2, -mc));
-                const float pr = (ml & (1u << TL_SLOT(r))) ? e : 0.f;      // unseen: exactly 0 whatever m is
-                sum += pr;
-                pf[r >> 3][r & 7] = (f16)pr;
-            }
-            l = fmaf(l, a, sum);
-            if (__any(moved)) {
-#pragma unroll
-                for (int db = 0; db < DB; ++db)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) o[db][r] *= a;
-            }
-            // ---- O^T[d][q] += V^T[d][slot] P^T[slot][q], k-slots as in the body file ----
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                const f16* vp = wV + tr_off + db * 32;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const f16x4 vl = lds_read_tr4(vp + (u * 16) * VSTR), vh = lds_read_tr4(vp + (u * 16 + 8) * VSTR);
-                    const f16x8 vf = {vl[0], vl[1], vl[2], vl[3], vh[0], vh[1], vh[2], vh[3]};
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[u], o[db], 0, 0, 0);
-                }
-            }
-            // ---- the next tile into the slot, after this tile's last LDS read ----
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            tile_store();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            if (!more) break;
-            kt = nk;
-            rest &= rest - 1u;
-        }
-        l += __shfl_xor(l, 32, 64);
-        const float inv = 1.0f / l;
-        if (q0 + l31 < Tq) {
-            f16* op = out + (qbase + (size_t)(q0 + l31) * HW) * ldo + head * D;
-#pragma unroll
-            for (int db = 0; db < DB; ++db)
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    f16x4 w;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) w[e] = (f16)(o[db][4 * qd + e] * inv);
-                    *(f16x4*)(op + db * 32 + 8 * qd + 4 * lh) = w;
-                }
-        }
-        tl = tl_next;
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) qf[kk] = qn[kk];
-    }
+    unsigned tl_next;                                              // the tiles of the next block
+#define TS_FIRST(t0)                        \
+    tl_next = tiles(0);                     \
+    const int kt0 = __builtin_ctz(tl_next); \
+    tile_load(t0, kt0, word(kt0));
+// the block's tiles tl, one 32-bit set (rest: those after kt); this lane's query g and its band slots (lo >= hi1: a query below
+// the anchor whose band lies inside it)
+#define TS_BLOCK(q0)                                                                  \
+    const unsigned tl = tl_next;                                                      \
+    tl_next = (q0) + 32 < Tq ? tiles((q0) + 32) : 0u;                                 \
+    const int g = q_frame0 + min((q0) + l31, Tq - 1);                                 \
+    const int lo = anchor + max(max(g - radius, anchor), band_frame0) - band_frame0;  \
+    const int hi1 = anchor + min(g + radius, hi_f) - band_frame0 + 1;
+#define TS_START                \
+    int kt = __builtin_ctz(tl); \
+    unsigned rest = tl & (tl - 1u);
+#define TS_NEXT(nt)                               \
+    const bool more = rest != 0u;                 \
+    const unsigned nxt = more ? rest : tl_next;   \
+    const int nk = nxt ? __builtin_ctz(nxt) : 0;  \
+    TemporalStreamTile<D> nt;                     \
+    tile_load(nt, nk, nxt ? word(nk) : 0u);
+#define TS_AND_WORD(kt) & word(kt)
+#define TS_ADVANCE \
+    kt = nk;       \
+    rest &= rest - 1u;
+#define TS_STORE(t) tile_store(t);
+#include "attn_temporal_stream_body.inc"
 }
 #undef TL_SLOT
+#undef TEMPORAL_WAVE_DECODE
+#undef TEMPORAL_LOAD_Q
+#undef TEMPORAL_STORE_O
 
 // waves per workgroup: as many as keep a workgroup's LDS at or below 42 KB (D = 64) / 37 KB (D = 128), at least one
 template <int D_, int KT_>
@@ -1720,6 +1485,20 @@ static int temporal_long_dispatch(int head_dim, int T, F&& f) {
     return MOFA_EINVAL;
 }
 
+// the streaming kernels' instantiation of a call, the key tiles fixed by the kernel: f(TemporalLongGeom<D, KT>{})
+template <int KT, class F>
+static int temporal_stream_dispatch(int head_dim, F&& f) {
+    return head_dim == 64 ? f(TemporalLongGeom<64, KT>{}) : f(TemporalLongGeom<128, KT>{});
+}
+
+// the mask words of n key slots: word w of key_mask (NULL = every slot) with the bits at and above n cleared; 0 for a word that
+// begins at or above n, which is not read
+static uint32_t temporal_mask_word(const uint32_t* key_mask, int w, int n) {
+    const int left = n - 32 * w;                                    // slots of this word below n
+    const uint32_t below = left >= 32 ? 0xffffffffu : left > 0 ? (1u << left) - 1u : 0u;
+    return below ? (key_mask ? key_mask[w] : 0xffffffffu) & below : 0u;
+}
+
 // what the three entry points ask of their common arguments (the streaming entry: the same with its own longest clip)
 static bool temporal_long_args_ok(const void* q, const void* k, const void* v, const void* out, int nclips, int T, int HW, int heads,
                                   int head_dim, int ld, int ldkv, int ldo, int max_T = 128) {
@@ -1747,11 +1526,7 @@ extern "C" int mofa_attn_temporal_long_masked_f16(const void* q, const void* k, 
                                                   const uint32_t* key_mask, mofa_stream_t stream) {
     if (!temporal_long_args_ok(q, k, v, out, nclips, T, HW, heads, head_dim, ld, ldkv, ldo) || Tq < 1 || Tq > T) return MOFA_EINVAL;
     uint32_t m[4];
-    for (int w = 0; w < 4; ++w) {
-        const int n = T - 32 * w;                                   // slots of this word below T
-        const uint32_t below = n >= 32 ? 0xffffffffu : n > 0 ? (1u << n) - 1u : 0u;
-        m[w] = (key_mask ? key_mask[w] : 0xffffffffu) & below;
-    }
+    for (int w = 0; w < 4; ++w) m[w] = temporal_mask_word(key_mask, w, T);
     if ((m[0] | m[1] | m[2] | m[3]) == 0) return MOFA_EINVAL;
     const long long nseq = (long long)nclips * HW * heads;
     return temporal_long_dispatch(head_dim, T, [&](auto g) {
@@ -1806,13 +1581,12 @@ extern "C" int mofa_attn_temporal_stream_local_f16(const void* q, const void* k,
     if (!temporal_long_args_ok(q, k, v, out, nclips, T, HW, heads, head_dim, ld, ldkv, ldo, 1024)) return MOFA_EINVAL;
     if (radius < 0 || radius > 32 || anchor < 0 || anchor > 32 || anchor > T) return MOFA_EINVAL;
     const long long nseq = (long long)nclips * HW * heads;
-    const auto launch = [&](auto g) {
+    return temporal_stream_dispatch<4>(head_dim, [&](auto g) {
         using G = decltype(g);
         return launch_temporal_long<G, attn_temporal_stream_local_kernel<G::D, G::WPB>>(
             nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale,
             radius, anchor);
-    };
-    return head_dim == 64 ? launch(TemporalLongGeom<64, 4>{}) : launch(TemporalLongGeom<128, 4>{});
+    });
 }
 
 // the local rule for 1 <= T <= 1024 frames under ANY radius >= 0 and 0 <= anchor <= T, dense (radius >= T - 1) included
@@ -1825,13 +1599,12 @@ extern "C" int mofa_attn_temporal_stream_f16(const void* q, const void* k, const
     if (radius < 0 || anchor < 0 || anchor > T) return MOFA_EINVAL;
     if (radius > T - 1) radius = T - 1;
     const long long nseq = (long long)nclips * HW * heads;
-    const auto launch = [&](auto g) {
+    return temporal_stream_dispatch<1>(head_dim, [&](auto g) {
         using G = decltype(g);
         return launch_temporal_long<G, attn_temporal_stream_kernel<G::D, G::WPB>>(
             nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, T, HW, heads, ld, ldkv, ldo, scale,
             radius, anchor);
-    };
-    return head_dim == 64 ? launch(TemporalLongGeom<64, 1>{}) : launch(TemporalLongGeom<128, 1>{});
+    });
 }
 
 // the streaming walk for a frame shard (attn_temporal_stream_shard_kernel): Tq >= 1 query frames against 1 <= S <= 1024 key slots.
@@ -1859,21 +1632,15 @@ extern "C" int mofa_attn_temporal_stream_shard_f16(const void* q, const void* k,
     }
     TemporalShardWords words;
     uint32_t any = 0;
-    for (int w = 0; w < 32; ++w) {
-        const int n = S - 32 * w;                                   // slots of this word below S
-        const uint32_t below = n >= 32 ? 0xffffffffu : n > 0 ? (1u << n) - 1u : 0u;
-        words.w[w] = below ? (key_mask ? key_mask[w] : 0xffffffffu) & below : 0u;     // (words past ceil(S / 32) are not read)
-        any |= words.w[w];
-    }
+    for (int w = 0; w < 32; ++w) any |= words.w[w] = temporal_mask_word(key_mask, w, S);
     if (any == 0) return MOFA_EINVAL;
     const long long nseq = (long long)nclips * HW * heads;
-    const auto launch = [&](auto g) {
+    return temporal_stream_dispatch<1>(head_dim, [&](auto g) {
         using G = decltype(g);
         return launch_temporal_long<G, attn_temporal_stream_shard_kernel<G::D, G::WPB>>(
             nseq, (hipStream_t)stream, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, nseq, Tq, S, HW, heads, ld, ldkv, ldo,
             scale, radius, anchor, q_frame0, band_frame0, words);
-    };
-    return head_dim == 64 ? launch(TemporalLongGeom<64, 1>{}) : launch(TemporalLongGeom<128, 1>{});
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -468,6 +468,29 @@ def _attn_temporal_prologue(q, k, v, rows, heads, head_dim, scale, out):
     return lib, scale, out
 
 
+def _attn_temporal_launch(lib, name, row, q, k, v, out, nclips, frames, HW, heads, head_dim, scale, tail, pairs, rows):
+    """one timed launch of the temporal entry point ``name``(q, k, v, out, nclips, *frames, HW, heads, head_dim, the three leading
+    dimensions, scale, *tail, stream).  With ``TIMER`` set the launch is recorded under ``row``: flops for ``pairs()`` visible
+    (query, key) pairs and bytes for ``rows()`` query + key rows, each per clip and pixel (evaluated only then)."""
+    t0 = TIMER.start() if TIMER is not None else None
+    L.check(getattr(lib, name)(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, *frames, HW, heads, head_dim,
+                               _ld(q), _ld(k), _ld(out), scale, *tail, L.stream_ptr()), name)
+    if t0 is not None:
+        Cc = heads * head_dim
+        TIMER.stop(row, t0, flops=4.0 * pairs() * Cc * nclips * HW, nbytes=4.0 * nclips * rows() * HW * Cc)
+
+
+def _attn_temporal_local_rule(Tq, key_mask, local, dense=None):
+    """what the self-attention entry points with a per-query rule share: ``Tq`` / ``key_mask`` refused, ``local`` as (radius,
+    anchor); local=None is ``dense`` where the entry point has a dense form"""
+    if key_mask is not None or Tq is not None:
+        raise ValueError("local temporal attention takes no key_mask and no Tq: the gathered-key path of frame-sharded clips has "
+                         "no per-query mask")
+    if local is None and dense is None:
+        raise ValueError("local=(radius, anchor) is required; dense temporal attention is attn_temporal")
+    return dense if local is None else tuple(int(x) for x in local)
+
+
 def attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=None, Tq=None, key_mask=None):
     """k/v hold T frames per clip; q holds Tq <= T (Tq < T: frame-sharded clip with all-gathered K/V).  key_mask: bit j =
     key frame j exists (padding frames of uneven shards in the gathered buffer are masked, never read).
@@ -481,12 +504,8 @@ def attn_temporal(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, out=No
         return attn_temporal_stream(q, k, v, nclips, T, HW, heads, head_dim=head_dim, scale=scale, out=out)
     lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * Tq * HW, heads, head_dim, scale, out)
     if T > 32:
-        t0 = TIMER.start() if TIMER is not None else None
-        L.check(lib.mofa_attn_temporal_long_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, T, HW, heads, head_dim,
-                                                _ld(q), _ld(k), _ld(out), scale, L.stream_ptr()), "mofa_attn_temporal_long_f16")
-        if t0 is not None:
-            Cc = heads * head_dim
-            TIMER.stop("attn_temporal_long_kernel", t0, flops=4.0 * T * T * Cc * nclips * HW, nbytes=8.0 * nclips * T * HW * Cc)
+        _attn_temporal_launch(lib, "mofa_attn_temporal_long_f16", "attn_temporal_long_kernel", q, k, v, out, nclips, (T,), HW, heads,
+                              head_dim, scale, (), lambda: T * T, lambda: 2 * T)
     elif key_mask is None:
         L.check(lib.mofa_attn_temporal_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, Tq, T, HW, heads, head_dim,
                                            _ld(q), _ld(k), _ld(out), scale, L.stream_ptr()), "mofa_attn_temporal_f16")
@@ -511,15 +530,9 @@ def attn_temporal_sharded(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None
         if m < 0:
             raise ValueError("key_mask must be a non-negative integer")
         words = (C.c_uint32 * 4)(*[(m >> (32 * w)) & 0xffffffff for w in range(4)])     # (bits >= 128 are >= T: ignored)
-    t0 = TIMER.start() if TIMER is not None else None
-    L.check(lib.mofa_attn_temporal_long_masked_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, Tq, T, HW, heads, head_dim,
-                                                   _ld(q), _ld(k), _ld(out), scale, words, L.stream_ptr()),
-            "mofa_attn_temporal_long_masked_f16")
-    if t0 is not None:
-        Cc = heads * head_dim
-        live = T if key_mask is None else bin(int(key_mask) & ((1 << T) - 1)).count("1")
-        TIMER.stop("attn_temporal_long_kernel", t0, flops=4.0 * Tq * live * Cc * nclips * HW,
-                   nbytes=4.0 * nclips * (Tq + live) * HW * Cc)
+    live = lambda: T if key_mask is None else bin(int(key_mask) & ((1 << T) - 1)).count("1")
+    _attn_temporal_launch(lib, "mofa_attn_temporal_long_masked_f16", "attn_temporal_long_kernel", q, k, v, out, nclips, (Tq, T), HW,
+                          heads, head_dim, scale, (words,), lambda: Tq * live(), lambda: Tq + live())
     return out
 
 
@@ -531,20 +544,10 @@ def attn_temporal_local(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None, 
     gathered-key path of frame-sharded clips has no per-query mask.  K and V of all T frames must be finite: an invisible frame
     is still read and weighted by an exact 0.  An entry point of its own: ``attn_temporal`` / ``attn_temporal_sharded`` keep
     their signatures (the CPU stand-ins mirror them parameter for parameter)."""
-    if key_mask is not None or Tq is not None:
-        raise ValueError("local temporal attention takes no key_mask and no Tq: the gathered-key path of frame-sharded clips has "
-                         "no per-query mask")
-    if local is None:
-        raise ValueError("local=(radius, anchor) is required; dense temporal attention is attn_temporal")
-    radius, anchor = (int(x) for x in local)
+    radius, anchor = _attn_temporal_local_rule(Tq, key_mask, local)
     lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * T * HW, heads, head_dim, scale, out)
-    t0 = TIMER.start() if TIMER is not None else None
-    L.check(lib.mofa_attn_temporal_long_local_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, T, HW, heads, head_dim,
-                                                  _ld(q), _ld(k), _ld(out), scale, radius, anchor, L.stream_ptr()),
-            "mofa_attn_temporal_long_local_f16")
-    if t0 is not None:
-        Cc = heads * head_dim
-        TIMER.stop("attn_temporal_long_kernel", t0, flops=4.0 * T * T * Cc * nclips * HW, nbytes=8.0 * nclips * T * HW * Cc)
+    _attn_temporal_launch(lib, "mofa_attn_temporal_long_local_f16", "attn_temporal_long_kernel", q, k, v, out, nclips, (T,), HW, heads,
+                          head_dim, scale, (radius, anchor), lambda: T * T, lambda: 2 * T)
     return out
 
 
@@ -571,15 +574,9 @@ def attn_temporal_window(q, k, v, nclips, S, HW, heads, head_dim=64, scale=None,
     radius, anchor = (int(x) for x in local)
     Tq = S if Tq is None else Tq
     lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * Tq * HW, heads, head_dim, scale, out)
-    t0 = TIMER.start() if TIMER is not None else None
-    L.check(lib.mofa_attn_temporal_long_window_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, Tq, S, HW, heads, head_dim,
-                                                   _ld(q), _ld(k), _ld(out), scale, radius, anchor, int(q_frame0), int(band_frame0),
-                                                   L.stream_ptr()), "mofa_attn_temporal_long_window_f16")
-    if t0 is not None:
-        Cc = heads * head_dim
-        TIMER.stop("attn_temporal_long_kernel", t0,
-                   flops=4.0 * window_visible_keys(S, Tq, radius, anchor, int(q_frame0), int(band_frame0)) * Cc * nclips * HW,
-                   nbytes=4.0 * nclips * (Tq + S) * HW * Cc)
+    _attn_temporal_launch(lib, "mofa_attn_temporal_long_window_f16", "attn_temporal_long_kernel", q, k, v, out, nclips, (Tq, S), HW,
+                          heads, head_dim, scale, (radius, anchor, int(q_frame0), int(band_frame0)),
+                          lambda: window_visible_keys(S, Tq, radius, anchor, int(q_frame0), int(band_frame0)), lambda: Tq + S)
     return out
 
 
@@ -587,20 +584,10 @@ def attn_temporal_local_stream(q, k, v, nclips, T, HW, heads, head_dim=64, scale
     """``attn_temporal_local`` for clips of up to 1024 frames under a window of radius <= 32 and anchor <= min(T, 32), through
     mofa_attn_temporal_stream_local_f16: the same rule, the same parameters in the same order, the same refusals; four key
     tiles in LDS however long the clip is.  For T <= 128 it gives the bits of ``attn_temporal_local``."""
-    if key_mask is not None or Tq is not None:
-        raise ValueError("local temporal attention takes no key_mask and no Tq: the gathered-key path of frame-sharded clips has "
-                         "no per-query mask")
-    if local is None:
-        raise ValueError("local=(radius, anchor) is required; dense temporal attention is attn_temporal")
-    radius, anchor = (int(x) for x in local)
+    radius, anchor = _attn_temporal_local_rule(Tq, key_mask, local)
     lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * T * HW, heads, head_dim, scale, out)
-    t0 = TIMER.start() if TIMER is not None else None
-    L.check(lib.mofa_attn_temporal_stream_local_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, T, HW, heads, head_dim,
-                                                    _ld(q), _ld(k), _ld(out), scale, radius, anchor, L.stream_ptr()),
-            "mofa_attn_temporal_stream_local_f16")
-    if t0 is not None:
-        Cc = heads * head_dim
-        TIMER.stop("attn_temporal_stream_kernel", t0, flops=4.0 * T * min(T, 128) * Cc * nclips * HW, nbytes=8.0 * nclips * T * HW * Cc)
+    _attn_temporal_launch(lib, "mofa_attn_temporal_stream_local_f16", "attn_temporal_stream_kernel", q, k, v, out, nclips, (T,), HW,
+                          heads, head_dim, scale, (radius, anchor), lambda: T * min(T, 128), lambda: 2 * T)
     return out
 
 
@@ -615,19 +602,10 @@ def attn_temporal_stream(q, k, v, nclips, T, HW, heads, head_dim=64, scale=None,
     with radius >= 0 and 0 <= anchor <= T, or None = dense (every query sees every key).  The parameters of
     ``attn_temporal_local`` in the same order, with the same refusals of ``Tq`` / ``key_mask``.  K and V of all T frames must be
     finite.  Not bitwise the one-pass kernels' output where both apply (another summation order)."""
-    if key_mask is not None or Tq is not None:
-        raise ValueError("local temporal attention takes no key_mask and no Tq: the gathered-key path of frame-sharded clips has "
-                         "no per-query mask")
-    radius, anchor = (max(T - 1, 0), 0) if local is None else (int(x) for x in local)
+    radius, anchor = _attn_temporal_local_rule(Tq, key_mask, local, dense=(max(T - 1, 0), 0))
     lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * T * HW, heads, head_dim, scale, out)
-    t0 = TIMER.start() if TIMER is not None else None
-    L.check(lib.mofa_attn_temporal_stream_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, T, HW, heads, head_dim,
-                                              _ld(q), _ld(k), _ld(out), scale, radius, anchor, L.stream_ptr()),
-            "mofa_attn_temporal_stream_f16")
-    if t0 is not None:
-        Cc = heads * head_dim
-        TIMER.stop("attn_temporal_stream_kernel", t0, flops=4.0 * stream_visible_pairs(T, radius, anchor) * Cc * nclips * HW,
-                   nbytes=8.0 * nclips * T * HW * Cc)
+    _attn_temporal_launch(lib, "mofa_attn_temporal_stream_f16", "attn_temporal_stream_kernel", q, k, v, out, nclips, (T,), HW, heads,
+                          head_dim, scale, (radius, anchor), lambda: stream_visible_pairs(T, radius, anchor), lambda: 2 * T)
     return out
 
 
@@ -662,15 +640,10 @@ def attn_temporal_stream_shard(q, k, v, nclips, S, HW, heads, head_dim=64, scale
             raise ValueError(f"local=(radius, anchor) needs radius >= 0, got {radius}")
     Tq = S if Tq is None else Tq
     lib, scale, out = _attn_temporal_prologue(q, k, v, nclips * Tq * HW, heads, head_dim, scale, out)
-    t0 = TIMER.start() if TIMER is not None else None
-    L.check(lib.mofa_attn_temporal_stream_shard_f16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nclips, Tq, S, HW, heads, head_dim,
-                                                    _ld(q), _ld(k), _ld(out), scale, radius, anchor, int(q_frame0), int(band_frame0),
-                                                    words, L.stream_ptr()), "mofa_attn_temporal_stream_shard_f16")
-    if t0 is not None:
-        Cc = heads * head_dim
-        pairs = Tq * live if local is None else window_visible_keys(S, Tq, radius, anchor, int(q_frame0), int(band_frame0))
-        TIMER.stop("attn_temporal_stream_kernel", t0, flops=4.0 * pairs * Cc * nclips * HW,
-                   nbytes=4.0 * nclips * (Tq + live) * HW * Cc)
+    _attn_temporal_launch(lib, "mofa_attn_temporal_stream_shard_f16", "attn_temporal_stream_kernel", q, k, v, out, nclips, (Tq, S), HW,
+                          heads, head_dim, scale, (radius, anchor, int(q_frame0), int(band_frame0), words),
+                          lambda: Tq * live if local is None else window_visible_keys(S, Tq, radius, anchor, int(q_frame0), int(band_frame0)),
+                          lambda: Tq + live)
     return out
 
 
